@@ -8,17 +8,23 @@ AdamW lr 1e-4 betas (0.5, 0.999) wd 1e-5, gradient clip 1.0 -- configs/training/
 forward + VAE loss + backward + [gradient all-reduce] + non-finite zeroing + clip + AdamW.
 Synthetic MedMNIST-shaped data resident in HBM (x = randint(0,256)/255*2-1, random one-hot of 12).
 
-    python bench.py [--gpus N --steps K --warmup W --config c4|c5|c2|c3]
+    python bench.py [--gpus N --steps K --warmup W --config c4|c5|c2|c3] [--dump-outputs DIR] [--full]
         N > 1 without a launcher: bench.py spawns N rank processes itself (before anything touches
         the GPU), one per GPU, RCCL ("nccl") process group over 127.0.0.1
     torchrun --nproc-per-node N bench.py --gpus N ...   (the same, launched externally)
 
-Rank 0 prints ONE JSON line (value = images/s over all ranks, max-over-ranks timing), with
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs (--dump-outputs DIR:
+DIR/<name>.npy, float32, the same inputs and so the same arrays from run to run) and prints the line; its
+`roofline`, `cpu_baseline`, `configs` and `parity` are measured under --full only.
+
+Rank 0 prints ONE JSON line (value = images/s over all ranks, max-over-ranks timing), with --full also
   roofline:     the implicit-GEMM MFMA kernel family, live HIP-event timing of every launch in one
                 instrumented step after the timed region (algorithmic FLOPs = the reference's conv /
                 bmm FLOPs), peak = the 3xBF16 ceiling (bf16 dense MFMA 2.5 PF / 3 products)
   cpu_baseline: the CPU oracle (reference algorithm restated, tests-pinned) timed on this host on a
-                bounded sample (rank 0, N=1 only).
+                bounded sample (rank 0, N=1 only)
+  configs:      the other BASELINE configs (c1 / c2 / c3 / c5 / c4x) on the same GPU (N=1, no --config / --batch)
+  parity:       one step of the cvae_c4_full golden case against the reference's recorded outputs (same condition).
 """
 from __future__ import annotations
 
@@ -361,9 +367,42 @@ def ops_hbm_tags():
     return ops.HBM_TAGS
 
 
-def run_config(name, args, rank, world, dev, want_cpu=True, steps=None, warmup=None):
+DUMP_SAMPLE = 1 << 20        # elements kept of an output larger than this (a fixed, seeded sample of its flat view)
+DUMP_PARAM_SAMPLE = 1 << 12  # elements kept of each updated parameter tensor
+
+
+def _flat_sample(t, limit, gen):
+    """`t` flattened, in float32 on the host; of a tensor with more than `limit` elements a sample at `limit` flat
+    positions drawn from `gen` (seeded by the caller, so the positions are the same from run to run)."""
+    t = t.detach().reshape(-1)
+    if t.numel() > limit:
+        idx = torch.randint(0, t.numel(), (limit,), generator=gen)
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, mod, loss):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the model outputs of that step
+    (reconstruction, mean, logvar, z, ...: VAELightningModule._last_outputs) and the parameters it updated -- as
+    `path`/<name>.npy in float32. Outputs over DUMP_SAMPLE elements and every parameter tensor over DUMP_PARAM_SAMPLE
+    are stored as seeded samples of their flat views (about 25 MB in all for c4)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    gen = torch.Generator().manual_seed(20240)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    outs = mod._last_outputs if isinstance(mod._last_outputs, dict) else {}
+    for k in sorted(outs):
+        v = outs[k]
+        if torch.is_tensor(v) and v.is_floating_point():
+            np.save(os.path.join(path, f"{k}.npy"), _flat_sample(v, DUMP_SAMPLE, gen))
+    params = [_flat_sample(p, DUMP_PARAM_SAMPLE, gen) for _, p in sorted(mod.model.named_parameters())]
+    np.save(os.path.join(path, "params_after_step.npy"), np.concatenate(params))
+
+
+def run_config(name, args, rank, world, dev, want_cpu=True, steps=None, warmup=None, dump=None):
     """Build the config's model, warm up, time `args.steps` steps (barrier + synchronize on both sides, max over
-    ranks), then one instrumented step for the rooflines. Returns the measured fields of the JSON line."""
+    ranks), write the last timed step's outputs to `dump` (if given), then under --full one instrumented step for
+    the rooflines and the CPU baseline. Returns the measured fields of the JSON line."""
     import medvae_disentangled_multimodal_amd as M
     from medvae_disentangled_multimodal_amd import ddp, ops
     cfg = dict(CONFIGS[name])
@@ -413,11 +452,13 @@ def run_config(name, args, rank, world, dev, want_cpu=True, steps=None, warmup=N
         dt = float(t.item())
     loss_v = float(loss.detach())
     peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9  # HBM held by the step (caching allocator peak)
+    if dump and rank == 0:
+        dump_outputs(dump, mod, loss)
 
     roofline = None
     bf16 = cfg.get("precision", "32") == "bf16-mixed"
     exact = cfg.get("precision", "32") == "32-exact"
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         ops.PROFILE = []
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -432,7 +473,7 @@ def run_config(name, args, rank, world, dev, want_cpu=True, steps=None, warmup=N
     torch.cuda.empty_cache()
 
     cpu = None
-    if rank == 0 and world == 1 and want_cpu and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and want_cpu and not args.no_cpu_baseline:
         cpu = cpu_baseline_for(cfg)
     imgs = cfg["batch"] * world * n_steps
     return {"value": round(imgs / dt, 3), "unit": "images/s", "steps": n_steps, "warmup": n_warm,
@@ -610,17 +651,27 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
-                    help="one config alone (default: c4, plus the c2 / c3 / c5 / c4x block and the parity block at "
-                         "N=1; c4x = c4 in exact fp32)")
+                    help="one config alone (default: c4; with --full at N=1 also the c1 / c2 / c3 / c5 / c4x block and "
+                         "the parity block; c4x = c4 in exact fp32)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the instrumented step's rooflines, the CPU baseline, "
+                         "the other configs and the parity block, and the detail file (off: set up, warm up, time the "
+                         "steps, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (loss, model outputs, a sample of the updated "
+                         "parameters) as DIR/<name>.npy, float32")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch override (default: config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the instrumented step")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity block")
     ap.add_argument("--detail", action="store_true", help="per-shape GEMM launch timings on stderr")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python (no HIP-graph replay)")
-    ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="where the full record (all roofline tables and notes) is written; stdout carries the compact line")
+    ap.add_argument("--detail-out", default=os.path.join("bench_out", "bench_detail.json"),
+                    help="with --full: where the full record (all roofline tables and notes) is written; stdout carries "
+                         "the compact line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -638,8 +689,8 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     head = args.config or "c4"
-    full = args.config is None and world == 1 and args.batch is None
-    line = run_config(head, args, rank, world, dev)
+    full = args.full and args.config is None and world == 1 and args.batch is None
+    line = run_config(head, args, rank, world, dev, dump=args.dump_outputs)
     extra, parity = None, None
     if full:  # the other BASELINE configs on the same box, same clock (their own images/s; not summed)
         extra = {}
@@ -674,7 +725,8 @@ def main():
             out["configs"] = extra
         if parity is not None:
             out["parity"] = parity
-        out["detail_file"] = write_detail(out, args.detail_out)
+        if args.full:
+            out["detail_file"] = write_detail(out, args.detail_out)
         print(compact_line(out), flush=True)
     if world > 1:
         dist.barrier()

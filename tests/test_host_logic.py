@@ -1,5 +1,5 @@
 """Host-side logic that needs no GPU: `_target_` config instantiation against the reference's own
-YAML (when the reference checkout is present), parameter naming / init parity with the reference,
+YAML (tests/golden/ref_configs), parameter naming / init parity with the reference,
 schedulers, conv geometry and the flat parameter buffer layout."""
 import json
 import os
@@ -10,10 +10,9 @@ import torch
 from cases import CASES
 from golden_io import GOLDEN
 
-REF_CFG = "/root/reference/configs/model"
+REF_CFG = os.path.join(GOLDEN, "ref_configs", "model")  # the reference's configs/model/*.yaml, stored as fixtures
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference checkout not present")
 @pytest.mark.parametrize("fname", ["base_vae.yaml", "beta_vae.yaml", "conditional_vae.yaml"])
 def test_reference_model_yaml_instantiates(fname):
     from medvae_disentangled_multimodal_amd import config
