@@ -290,6 +290,26 @@ int mvae_attention_small_fwd(const float* q, const float* k, const float* v, flo
 int mvae_attention_small_bwd(const float* q, const float* k, const float* v, const float* dout, const float* lse,
                              float* dq, float* dk, float* dv, int batch, int n, int c, float scale, void* stream);
 
+/* Linear attention core (LinearAttention / LinAttnBlock with heads = 1, encoder_decoder.py:36-65): the memory-bound
+ * stages around the batched GEMMs ctx = softmax_n(k)^T v and o = q ctx (mvae_gemm_strided_batched). q, k, v are the
+ * channel slices [0:c], [c:2c], [2c:3c] of one NHWC tensor [batch][n][3c], read in place: k = the k slice's first
+ * element, ldk = 3c, stride_k = 3c n. Contract: any n >= 1, c % 4 == 0, 16-B aligned pointers, ld / stride % 4 == 0,
+ * batch <= 65535. All fp32; the reductions merge (max, sum) pairs in a fixed order (no atomics).
+ *   kstats:   stats [batch][2][c] = per (image, channel) max m over the n tokens and 1 / sum_n exp(k - m); the tokens
+ *             are split across workgroups within workspace (mvae_linattn_workspace_bytes)
+ *   ksoftmax: ksm [batch][n][c] = exp(k - m) / Z (compact)
+ *   dk:       dk ([batch][n] rows of c at lddk / stride_dk) holds dksm = v dctx^T on entry and
+ *             dk = ksm o (dksm - r) on return, ksm recomputed from k and stats, r[d] = sum_n ksm[n][d] dksm[n][d]
+ *             (a column reduction like kstats, within workspace: mvae_linattn_workspace_bytes) */
+size_t mvae_linattn_workspace_bytes(int batch, int n, int c);
+int mvae_linattn_kstats(const float* k, long long ldk, long long stride_k, float* stats, int batch, int n, int c,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int mvae_linattn_ksoftmax(const float* k, long long ldk, long long stride_k, const float* stats, float* ksm, int batch,
+                          int n, int c, void* stream);
+int mvae_linattn_dk(const float* k, long long ldk, long long stride_k, const float* stats, float* dk, long long lddk,
+                    long long stride_dk, int batch, int n, int c, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* Query-block fused attention for 64 <= n <= 256 tokens, n % 64 == 0, c % 128 == 0 (c4 / c5's 16x16 AttnBlocks and the
  * 8x8 mid blocks at C = 2048, encoder_decoder.py:83-107): one workgroup per (64-query block, image).
  * fwd: o = softmax(q k^T * scale, dim=2) v in one launch; p [batch][n][n] receives P (the backward's saved tensor).

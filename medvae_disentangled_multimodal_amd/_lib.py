@@ -77,6 +77,10 @@ SIGNATURES = {
     "mvae_attention_small_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, F, P]),
     "mvae_attention_tile_fwd": (I, [P, P, P, P, P, I, I, I, F, P]),
     "mvae_attention_tile_bwd": (I, [P, P, P, P, P, P, I, I, I, F, P]),
+    "mvae_linattn_workspace_bytes": (Z, [I, I, I]),
+    "mvae_linattn_kstats": (I, [P, L, L, P, I, I, I, P, Z, P]),
+    "mvae_linattn_ksoftmax": (I, [P, L, L, P, P, I, I, I, P]),
+    "mvae_linattn_dk": (I, [P, L, L, P, P, L, L, I, I, I, P, Z, P]),
     "mvae_group_norm_fwd_nhwc": (I, [P, P, P, P, P, P, I, I, I, I, F, I, F, c_uint64, I, P, Z, P]),
     "mvae_group_norm_fwd_part_nhwc": (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, F, c_uint64, I, P, Z, P]),
     "mvae_group_norm_bwd_nhwc": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, c_uint64, P, Z, P]),

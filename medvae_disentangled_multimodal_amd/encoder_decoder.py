@@ -8,6 +8,8 @@ The forward composes the fused HIP ops of `ops.py`:
   ResnetBlock  = GN+SiLU -> conv3x3 -> GN+SiLU(+dropout) -> conv3x3 with the skip add (or the
                  1x1 nin_shortcut output) fused into the second conv's epilogue
   AttnBlock    = GN -> q/k/v 1x1 GEMMs -> attention core -> proj_out GEMM (+x fused)
+  LinAttnBlock = bias-free q/k/v 1x1 GEMM -> linear attention core on the channel slices -> to_out GEMM (no norm,
+                 no skip)
   Downsample   = stride-2 conv whose zero fill covers the (0,1,0,1) F.pad
   Upsample     = conv whose gather reads the nearest-x2 upsampled image without materialising it
 """
@@ -143,10 +145,36 @@ class AttnBlock(nn.Module):
         return self.proj_out(o, residual=x, res_sink=sink)
 
 
+class LinearAttention(nn.Module):
+    """encoder_decoder.py:36-58: a bias-free 1x1 conv to q, k, v (output channels qkv-major), softmax of k over the
+    tokens, context = k v^T, out = context^T q, 1x1 conv out. No norm and no skip: the output replaces x. The HIP core
+    (ops.linear_attention_core) reads q, k, v as channel slices of to_qkv's NHWC output; it covers one head."""
+
+    def __init__(self, dim: int, heads: int = 4, dim_head: int = 32):
+        super().__init__()
+        self.heads = heads
+        hidden_dim = dim_head * heads
+        self.to_qkv = Conv2d(dim, hidden_dim * 3, 1, bias=False)
+        self.to_out = Conv2d(hidden_dim, dim, 1)
+
+    def forward(self, x):
+        if self.heads != 1:
+            raise NotImplementedError(f"LinearAttention with heads={self.heads} is not on the MI355X path: the HIP core "
+                                      "covers heads=1 (LinAttnBlock)")
+        return self.to_out(ops.linear_attention_core(self.to_qkv(x)))
+
+
+class LinAttnBlock(LinearAttention):
+    def __init__(self, in_channels: int):
+        super().__init__(dim=in_channels, heads=1, dim_head=in_channels)
+
+
 def make_attn(in_channels: int, attn_type: str = "vanilla") -> nn.Module:
     if attn_type == "vanilla":
         return AttnBlock(in_channels)
-    raise NotImplementedError(f"attention type {attn_type!r} is not on the MI355X path (only 'vanilla')")
+    if attn_type == "linear":
+        return LinAttnBlock(in_channels)
+    raise NotImplementedError(f"attention type {attn_type!r} is not on the MI355X path (only 'vanilla' and 'linear')")
 
 
 class Downsample(nn.Module):

@@ -2053,6 +2053,104 @@ def attention_core(q, k, v):
 
 
 # ------------------------------------------------------------------------------------------
+# linear attention core: q (softmax_tokens(k)^T v) over the h*w tokens of each image
+# ------------------------------------------------------------------------------------------
+def _la_gemm(ta, tb, m, n, k, A, lda, sA, B, ldb, sB, C, ldc, sC, batch, st, dev, split_k=False):
+    """one batched GEMM of the linear attention core on raw pointers (q / k / v and their gradients are channel slices
+    of one [b, n, 3C] tensor); split_k: the C x C products over the tokens split K within an arena workspace"""
+    ws, nbytes = None, 0
+    if split_k:
+        nbytes = _lib.query("mvae_gemm_workspace_bytes", m, n, k, batch)
+        if nbytes:
+            ws = ARENA.get("ws", nbytes, dev)
+            nbytes = ws.numel()
+    with _timed("attn_gemm", 2.0 * m * n * k * batch, (m, n, k, batch)):
+        _lib.call("mvae_gemm_strided_batched", ta, tb, m, n, k, 1.0, A, lda, sA, B, ldb, sB, 0.0, C, ldc, sC, batch,
+                  None, None, 0, 0, _ptr(ws), nbytes, st)
+
+
+def _la_ksoftmax(qkv, stats, b, n, c, st, with_stats: bool):
+    """softmax of the k slice over the tokens as a compact [b, n, C] arena scratch (current stream only)"""
+    kp = qkv.data_ptr() + 4 * c
+    dev = qkv.device
+    if with_stats:
+        ws = ARENA.get("linattn_ws", _lib.query("mvae_linattn_workspace_bytes", b, n, c), dev)
+        _lib.call("mvae_linattn_kstats", kp, 3 * c, 3 * c * n, stats.data_ptr(), b, n, c, ws.data_ptr(), ws.numel(), st)
+    ksm = ARENA.get("linattn_ksm", 4 * b * n * c, dev)
+    _lib.call("mvae_linattn_ksoftmax", kp, 3 * c, 3 * c * n, stats.data_ptr(), ksm.data_ptr(), b, n, c, st)
+    return ksm
+
+
+class LinAttnCoreFn(torch.autograd.Function):
+    """LinearAttention with one head (encoder_decoder.py:46-57): out[e][n] = sum_d ctx[d][e] q[d][n] with
+    ctx[d][e] = sum_n softmax_n(k)[d][n] v[e][n]. qkv [b, 3C, h, w] channels_last holds q, k, v as channel slices, read
+    in place (leading dimension 3C). Forward: column statistics of k, ksm = softmax(k) as a scratch operand, two batched
+    GEMMs (4 n C^2 b FLOP); saved: qkv, ctx [b, C, C] and the statistics [b, 2, C]. Backward: ksm recomputed, four GEMMs
+    writing dq / dksm / dv into the slices of one [b, 3C, h, w] gradient, dk = ksm o (dksm - colsum(ksm o dksm)) in
+    place (csrc/linattn.hip). Nothing of size n x n exists."""
+
+    @staticmethod
+    def forward(ctx, qkv):
+        _check(qkv, "linear attention qkv")
+        if qkv.dim() != 4 or qkv.shape[1] % 3 != 0:
+            raise RuntimeError(f"linear attention: qkv must be [b, 3C, h, w], got {tuple(qkv.shape)}")
+        qkv = nhwc(qkv)
+        if not _al16(qkv):
+            qkv = qkv.clone(memory_format=CL)
+        b, c3, h, w = qkv.shape
+        c, n = c3 // 3, h * w
+        if c % 4 != 0:
+            raise RuntimeError(f"linear attention: C = {c} breaks the kernel contract C % 4 == 0 (16-byte q / k / v slices)")
+        st, dev = _stream(qkv), qkv.device
+        ctx.math = _MATH[0]
+        stats = torch.empty((b, 2, c), device=dev, dtype=torch.float32)
+        cx = torch.empty((b, c, c), device=dev, dtype=torch.float32)
+        o = torch.empty((b, c, h, w), device=dev, dtype=torch.float32, memory_format=CL)
+        qp = qkv.data_ptr()
+        ksm = _la_ksoftmax(qkv, stats, b, n, c, st, True)
+        # ctx = ksm^T V (K = n), O = Q ctx (K = C)
+        _la_gemm(1, 0, c, c, n, ksm.data_ptr(), c, n * c, qp + 8 * c, 3 * c, 3 * c * n, cx.data_ptr(), c, c * c, b, st, dev,
+                 split_k=True)
+        _la_gemm(0, 0, n, c, c, qp, 3 * c, 3 * c * n, cx.data_ptr(), c, c * c, o.data_ptr(), c, n * c, b, st, dev)
+        ctx.save_for_backward(qkv, cx, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        with math_scope(ctx.math):
+            return LinAttnCoreFn._backward(ctx, do)
+
+    @staticmethod
+    def _backward(ctx, do):
+        qkv, cx, stats = ctx.saved_tensors
+        b, c3, h, w = qkv.shape
+        c, n = c3 // 3, h * w
+        do = nhwc(do)
+        if not _al16(do):
+            do = do.clone(memory_format=CL)
+        st, dev = _stream(qkv), qkv.device
+        dqkv = torch.empty_like(qkv, memory_format=CL)
+        dcx = torch.empty_like(cx)
+        qp, gp, dop = qkv.data_ptr(), dqkv.data_ptr(), do.data_ptr()
+        l3, s3 = 3 * c, 3 * c * n
+        # dctx = Q^T dO (K = n), dQ = dO ctx^T
+        _la_gemm(1, 0, c, c, n, qp, l3, s3, dop, c, n * c, dcx.data_ptr(), c, c * c, b, st, dev, split_k=True)
+        _la_gemm(0, 1, n, c, c, dop, c, n * c, cx.data_ptr(), c, c * c, gp, l3, s3, b, st, dev)
+        ksm = _la_ksoftmax(qkv, stats, b, n, c, st, False)
+        # dV = ksm dctx, dksm = V dctx^T (into the k slice, turned into dk in place)
+        _la_gemm(0, 0, n, c, c, ksm.data_ptr(), c, n * c, dcx.data_ptr(), c, c * c, gp + 8 * c, l3, s3, b, st, dev)
+        _la_gemm(0, 1, n, c, c, qp + 8 * c, l3, s3, dcx.data_ptr(), c, c * c, gp + 4 * c, l3, s3, b, st, dev)
+        ws = ARENA.get("linattn_ws", _lib.query("mvae_linattn_workspace_bytes", b, n, c), dev)
+        _lib.call("mvae_linattn_dk", qp + 4 * c, l3, s3, stats.data_ptr(), gp + 4 * c, l3, s3, b, n, c, ws.data_ptr(),
+                  ws.numel(), st)
+        return dqkv
+
+
+def linear_attention_core(qkv):
+    return LinAttnCoreFn.apply(qkv)
+
+
+# ------------------------------------------------------------------------------------------
 # reparameterization, KL, reconstruction
 # ------------------------------------------------------------------------------------------
 def _pixel_ld(t: torch.Tensor) -> Optional[int]:
