@@ -449,12 +449,14 @@ int mvae_loss_combine4_bwd(const float* flags, float w0, float w1, float w2, flo
 
 /* ---- optimizer step over one flat buffer ----------------------------------------------------------
  * on_before_optimizer_step (lightning_module.py:468-477) + configure_gradient_clipping (:452-466) +
- * Adam/AdamW (configure_optimizers, :390-408). scalars[0] = total grad norm, scalars[1] = coef. */
+ * Adam/AdamW (configure_optimizers, :390-408). scalars[0] = total grad norm, scalars[1] = coef.
+ * lr, the betas and the weight decay are doubles: torch forms 1 - beta, lr / (1 - beta1^step) and 1 - lr * wd from
+ * Python floats and rounds to fp32 once. */
 int mvae_multi_tensor_adam(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                            const int* chunk_tensor, const long long* chunk_start, const int* chunk_len,
                            int nchunks, const int* tensor_chunk_begin, int ntensors, const int* used,
-                           int* step, float grad_scale, float max_norm, int do_clip, float lr, float beta1,
-                           float beta2, float eps, float weight_decay, int decoupled, void* workspace,
+                           int* step, float grad_scale, float max_norm, int do_clip, double lr, double beta1,
+                           double beta2, float eps, double weight_decay, int decoupled, void* workspace,
                            size_t workspace_bytes, float* scalars, void* stream);
 size_t mvae_multi_tensor_adam_workspace_bytes(int nchunks, int ntensors);
 

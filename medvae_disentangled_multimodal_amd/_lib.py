@@ -107,7 +107,7 @@ SIGNATURES = {
     "mvae_loss_combine4_fwd": (I, [P, P, P, P, F, F, F, F, I, F, P, P, P, P, P, P, P]),
     "mvae_loss_combine4_bwd": (I, [P, F, F, F, F, I, P, P, P, P, P, P, P]),
     "mvae_recon_bwd": (I, [I, P, P, P, D, P, L, P]),
-    "mvae_multi_tensor_adam": (I, [P, P, P, P, P, P, P, I, P, I, P, P, F, F, I, F, F, F, F, F, I, P, Z, P, P]),
+    "mvae_multi_tensor_adam": (I, [P, P, P, P, P, P, P, I, P, I, P, P, F, F, I, D, D, D, F, D, I, P, Z, P, P]),
     "mvae_multi_tensor_adam_workspace_bytes": (Z, [I, I]),
     "mvae_lpips_scale": (I, [P, P, L, I, F, F, P, P, P]),
     "mvae_lpips_scale_bwd": (I, [P, P, L, I, F, P, P]),

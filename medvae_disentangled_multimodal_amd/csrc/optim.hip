@@ -91,8 +91,13 @@ __global__ void __launch_bounds__(256) mt_finalize_kernel(MtArgs a, float max_no
   }
 }
 
-__global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, float lr, float b1, float b2, float eps, float wd,
+// w = 1 - beta1 and omb2 = 1 - beta2 come rounded from the double difference, as torch forms them (1 - 0.999 -> 0.001f):
+// 1.f - 0.999f is 0.00099998713, 1.3e-5 off, and exp_avg_sq carried that error in every element
+// ... and the bias corrections 1 - beta^step from the double betas (torch: Python floats), consistent with them; the
+// step size lr / bias_correction1 and the decoupled decay 1 - lr * wd likewise from the double lr and weight decay
+__global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, double lr, double b1d, double b2d, float eps, double wdd,
                                                       int decoupled) {
+  const float b2 = (float)b2d, w = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d), wd = (float)wdd;
   const int ch = blockIdx.x;
   const int t = a.chunk_tensor[ch];
   if (!a.used[t]) return;
@@ -101,12 +106,11 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, float lr, float 
   const bool zero = a.bad[t] != 0;
   const float coef = a.scalars[1];
   const int step = a.step[t];
-  const double bc1 = 1.0 - pow((double)b1, (double)step);
-  const double bc2 = 1.0 - pow((double)b2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
+  const double bc1 = 1.0 - pow(b1d, (double)step);
+  const double bc2 = 1.0 - pow(b2d, (double)step);
+  const float step_size = (float)(lr / bc1);
   const float bc2_sqrt = (float)sqrt(bc2);
-  const float decay = (float)(1.0 - (double)lr * (double)wd);
-  const float w = 1.f - b1;
+  const float decay = (float)(1.0 - lr * wdd);
   // one element of the update (torch.optim.Adam/AdamW single-tensor arithmetic, in its operation order)
   auto upd = [&](float g, float& p, float& m, float& v) -> float {
     g = zero ? 0.f : g * a.gscale;
@@ -115,7 +119,7 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, float lr, float 
     if (decoupled) p = p * decay;
     else if (wd != 0.f) g = g + wd * p;
     m = (w < 0.5f) ? m + w * (g - m) : g - (g - m) * (1.f - w);
-    v = v * b2 + (1.f - b2) * g * g;
+    v = v * b2 + omb2 * g * g;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     p = p + (-step_size) * (m / denom);
     return gout;
@@ -145,7 +149,7 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, float lr, float 
     else if (wd != 0.f) g = g + wd * p;
     float m = a.m[e];
     m = (w < 0.5f) ? m + w * (g - m) : g - (g - m) * (1.f - w);
-    float v = a.v[e] * b2 + (1.f - b2) * g * g;
+    float v = a.v[e] * b2 + omb2 * g * g;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     p = p + (-step_size) * (m / denom);
     a.m[e] = m;
@@ -166,8 +170,8 @@ extern "C" {
 int mvae_multi_tensor_adam(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int* chunk_tensor,
                            const long long* chunk_start, const int* chunk_len, int nchunks,
                            const int* tensor_chunk_begin, int ntensors, const int* used, int* step, float grad_scale,
-                           float max_norm, int do_clip, float lr, float beta1, float beta2, float eps,
-                           float weight_decay, int decoupled, void* workspace, size_t workspace_bytes, float* scalars,
+                           float max_norm, int do_clip, double lr, double beta1, double beta2, float eps,
+                           double weight_decay, int decoupled, void* workspace, size_t workspace_bytes, float* scalars,
                            void* stream) {
   const size_t need = (size_t)nchunks * (sizeof(double) + sizeof(int)) + (size_t)ntensors * sizeof(int) + 64;
   if (nchunks <= 0 || ntensors <= 0) { set_error("adam: empty"); return MVAE_EINVAL; }
