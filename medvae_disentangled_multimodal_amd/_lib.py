@@ -75,8 +75,6 @@ SIGNATURES = {
     "mvae_softmax_rows_bwd": (I, [P, P, P, L, I, P]),
     "mvae_attention_small_fwd": (I, [P, P, P, P, P, I, I, I, F, P]),
     "mvae_attention_small_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, F, P]),
-    "mvae_attention_tile_fwd": (I, [P, P, P, P, P, I, I, I, F, P]),
-    "mvae_attention_tile_bwd": (I, [P, P, P, P, P, P, I, I, I, F, P]),
     "mvae_linattn_workspace_bytes": (Z, [I, I, I]),
     "mvae_linattn_kstats": (I, [P, L, L, P, I, I, I, P, Z, P]),
     "mvae_linattn_ksoftmax": (I, [P, L, L, P, P, I, I, I, P]),

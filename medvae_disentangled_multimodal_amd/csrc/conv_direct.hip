@@ -155,8 +155,8 @@ int mvae_conv2d_direct32_nhwc(const float* x, const float* w, const float* bias,
     set_error("conv2d_direct32: 32 -> 32 channels, W <= 62, aligned x / w; dgrad: no bias / residual / split weights");
     return MVAE_EINVAL;
   }
-  static const bool big_env = getenv("MVAE_CD_BIG") != nullptr;  // experiment knob: 8-wave workgroups, one per CU
-  const bool big = big_env || 3 * (wd + 2) + 2 + 16 > 208;      // (a band of one row does not fit the small image)
+  // 8-wave workgroups, one per CU, when a band of one row does not fit the small image
+  const bool big = 3 * (wd + 2) + 2 + 16 > 208;
   const int maxpix = big ? 384 : 208;
   CdArgs a{};
   a.x = x; a.w = w; a.bias = bias; a.res = residual; a.y = y;

@@ -1914,7 +1914,7 @@ __device__ __forceinline__ void splitk_reduce4_rows(const GemmArgs& a, int bx, i
 // ------------------------------------------------------------------------------------------
 // host-side dispatch
 // ------------------------------------------------------------------------------------------
-enum { T256x256 = 0, T256x128 = 1, T128x256 = 2, T128x128 = 3, T64x64 = 4, T128x16 = 5, T128x32 = 6 };
+enum { T256x256 = 0, T256x128 = 1, T128x256 = 2, T128x128 = 3, T64x64 = 4, T128x16 = 5 };
 
 // process-wide GEMM arithmetic (mvae_set_math_mode): 3xBF16 fp32 emulation (default), bf16, or exact fp32
 // on the f32-input MFMA (v_mfma_f32_{16x16x4,32x32x2}_f32: 1/16 of the bf16 rate)
@@ -1922,24 +1922,24 @@ enum { MATH_3XBF16 = 0, MATH_BF16 = 1, MATH_FP32 = 2 };
 int math_mode();
 
 // workgroups of a tile config resident per CU at once (LDS-bound: 160, 120, 120, 80, 40 KB per workgroup; the skinny
-// tiles 4 / 3): a "round" of a launch is 256 CUs x this many tiles
+// tile 4): a "round" of a launch is 256 CUs x this many tiles
 inline int resident_of(int cfg) {
-  static const int r[7] = {1, 1, 1, 2, 4, 4, 3};
-  return (cfg >= 0 && cfg < 7) ? r[cfg] : 1;
+  static const int r[6] = {1, 1, 1, 2, 4, 4};
+  return (cfg >= 0 && cfg < 6) ? r[cfg] : 1;
 }
 // tile edge lengths of a config (rows of M, columns of N)
 inline int tile_m_of(int cfg) {
-  static const int m[7] = {256, 256, 128, 128, 64, 128, 128};
-  return (cfg >= 0 && cfg < 7) ? m[cfg] : 64;
+  static const int m[6] = {256, 256, 128, 128, 64, 128};
+  return (cfg >= 0 && cfg < 6) ? m[cfg] : 64;
 }
 inline int tile_n_of(int cfg) {
-  static const int n[7] = {256, 128, 256, 128, 64, 16, 32};
-  return (cfg >= 0 && cfg < 7) ? n[cfg] : 64;
+  static const int n[6] = {256, 128, 256, 128, 64, 16};
+  return (cfg >= 0 && cfg < 6) ? n[cfg] : 64;
 }
 
 inline long long tiles_of(int cfg, const GemmArgs& a) {
-  static const int TM_[] = {256, 256, 128, 128, 64, 128, 128};
-  static const int TN_[] = {256, 128, 256, 128, 64, 16, 32};
+  static const int TM_[] = {256, 256, 128, 128, 64, 128};
+  static const int TN_[] = {256, 128, 256, 128, 64, 16};
   return (long long)cdiv(a.M, TM_[cfg]) * cdiv(a.N, TN_[cfg]) * a.batch;
 }
 
@@ -1961,11 +1961,6 @@ inline int tile_override() {
   return v;
 }
 
-inline bool tile_rule_legacy() {  // experiment knob: MVAE_TILE_LEGACY=1 restores the >= 240-tiles rule
-  static int v = getenv("MVAE_TILE_LEGACY") != nullptr;
-  return v != 0;
-}
-
 inline int choose_tile(const GemmArgs& a, bool allow_big, bool can_split) {
   const int ov = tile_override();
   if (ov >= 0 && ov <= 4 && (allow_big || ov >= T128x128)) return ov;
@@ -1973,13 +1968,7 @@ inline int choose_tile(const GemmArgs& a, bool allow_big, bool can_split) {
   // skinny N (Decoder.conv_out forward, cout 3; Encoder.conv_in input gradient, cin 6): 128x16 tiles on
   // 2 waves instead of 64-wide tiles that are 95 % padding
   if (allow_big && a.N <= 16 && tiles_of(T128x16, a) >= 512) return T128x16;
-  // 32-wide N (the 28x28 level of the c3 model at 32 channels, fwd and input gradient): 128x32 tiles on 4 waves
-  // (32x32 per wave) instead of 64x64 tiles whose second half of N is padding. Opt-in (MVAE_T128X32=1): measured on c3
-  // (same box) the forward launches ran 17 % slower (2.24 -> 2.62 ms per step), the input gradient unchanged.
-  static const bool t128x32 = getenv("MVAE_T128X32") != nullptr;
-  if (t128x32 && allow_big && !can_split && a.N > 16 && a.N <= 32 && tiles_of(T128x32, a) >= 512 && !tile_rule_legacy())
-    return T128x32;
-  if (allow_big && !can_split && !tile_rule_legacy()) {
+  if (allow_big && !can_split) {
     // Cost model over the tile configs (fwd / dgrad / batched GEMMs; split-K GEMMs keep the rule below):
     // time ~ rounds x (tiles resident per CU) x tile area / per-tile efficiency, with rounds =
     // ceil(tiles / (256 CUs x tiles resident per CU)). Efficiencies are the measured full-chip rates of each
@@ -2029,12 +2018,12 @@ template <int CFG, int AK, int VA, int BKIND, int VB, int PO = -1>
 void launch_cfg(GemmArgs& a, hipStream_t st) {
   constexpr int BM = CFG == T256x256 || CFG == T256x128 ? 256 : CFG == T64x64 ? 64 : 128;
   constexpr int BN = CFG == T256x256 || CFG == T128x256 ? 256 : CFG == T64x64 ? 64 : CFG == T128x16 ? 16
-                   : CFG == T128x32 ? 32 : 128;
-  constexpr int WGM = CFG == T256x128 || CFG == T128x32 ? 4 : 2;
+                   : 128;
+  constexpr int WGM = CFG == T256x128 ? 4 : 2;
 #ifdef MVAE_W4
-  constexpr int WGN = CFG == T128x256 ? 4 : (CFG == T128x16 || CFG == T128x32) ? 1 : 2;  // 256x256 on 4 waves
+  constexpr int WGN = CFG == T128x256 ? 4 : CFG == T128x16 ? 1 : 2;  // 256x256 on 4 waves
 #else
-  constexpr int WGN = (CFG == T256x256 || CFG == T128x256) ? 4 : (CFG == T128x16 || CFG == T128x32) ? 1 : 2;
+  constexpr int WGN = (CFG == T256x256 || CFG == T128x256) ? 4 : CFG == T128x16 ? 1 : 2;
 #endif
   a.tiles_m = cdiv(a.M, BM);
   a.tiles_n = cdiv(a.N, BN);
@@ -2070,10 +2059,6 @@ void launch_big(GemmArgs& a, hipStream_t st, int cfg) {
     case T128x128: launch_cfg<T128x128, AK, VA, BKIND, VB>(a, st); break;
     case T128x16:  // 16-wide tiles need the 16x16x32 MFMA shape
       if constexpr (mf_of(AK) == 16) launch_cfg<T128x16, AK, VA, BKIND, VB>(a, st);
-      else launch_cfg<T64x64, AK, VA, BKIND, VB>(a, st);
-      break;
-    case T128x32:  // (the same)
-      if constexpr (mf_of(AK) == 16 && VA == 4 && VB == 4) launch_cfg<T128x32, AK, VA, BKIND, VB>(a, st);
       else launch_cfg<T64x64, AK, VA, BKIND, VB>(a, st);
       break;
     default: launch_cfg<T64x64, AK, VA, BKIND, VB>(a, st); break;
@@ -2122,18 +2107,11 @@ inline void set_splits(GemmArgs& a, int splits) {
 // 64x64 / 128x16): a small-tile split-K GEMM (c3's wgrad of 32-128 channels: M x N = 32 x 288 .. 128 x 1152,
 // K = 25k-400k pixels) with one workgroup per CU runs its K loop latency-bound (one tile in flight per CU).
 constexpr int MAX_SPLITS = 256;
-inline bool split_res_legacy() {  // experiment knob: MVAE_SPLIT_LEGACY=1 restores one-workgroup-per-CU rounds
-  static int v = getenv("MVAE_SPLIT_LEGACY") != nullptr;
-  return v != 0;
-}
 inline int choose_splits(const GemmArgs& a, int cfg) {
-  static const int res_of[7] = {1, 1, 1, 2, 4, 4, 3};
-  const bool legacy = split_res_legacy();
-  const int res = legacy ? 1 : res_of[cfg];
-  const long long slots = 256LL * res;
+  static const int res_of[6] = {1, 1, 1, 2, 4, 4};
+  const long long slots = 256LL * res_of[cfg];
   const long long tiles = tiles_of(cfg, a);
-  const int ms = legacy ? std::max(1, (int)std::min<long long>(64, a.K / 512))
-                        : std::max(1, (int)std::min<long long>(MAX_SPLITS, a.K / 256));
+  const int ms = std::max(1, (int)std::min<long long>(MAX_SPLITS, a.K / 256));
   if (tiles >= 4 * slots) return 1;
   int best = 1;
   double best_eff = -1.0;

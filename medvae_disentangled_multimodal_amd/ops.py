@@ -943,14 +943,13 @@ def split_dy(dy: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=None, dkeep=None, out=None,
-                     beta: float = 0.0, u_pre=None):
+                     beta: float = 0.0):
     """gn_link (GnBwdLink): the conv's input was silu?(GroupNorm(x)) -- also emit that GroupNorm's backward
     partials from the GEMM epilogue (mvae_conv2d_dgrad_gnbwd_nhwc) into gn_link.part when the launch allows it.
     dys: dy pre-split by split_dy (same values; used as the gathered GEMM operand when given).
     dyb: dy as packed bf16 (pack_dy; bf16-mixed mode).
     dkeep (a list): on the Winograd path also keep the weight gradient's transformed dy per image chunk (_winograd).
-    out / beta (1x1 convs only): dx = beta * out + dy W into out (DxSum).
-    u_pre ((U', event)): the Winograd filter transform computed during the forward on a side stream (_upre_launch)."""
+    out / beta (1x1 convs only): dx = beta * out + dy W into out (DxSum)."""
     n, c, h, wd = x_shape
     co = w.shape[0]
     _, _, ho, wo = dy.shape
@@ -998,9 +997,6 @@ def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=No
         part = torch.empty(n * h * wd // 32 * c * 2, device=dy.device, dtype=torch.float64) if link else None
         with _timed("conv_dgrad", _wino_alg(flops), shp, flops):
             u = None
-            if u_pre is not None:  # (made during the forward on the side stream: joined here)
-                torch.cuda.current_stream(dy.device).wait_event(u_pre[1])
-                u = u_pre[0]
             for b0, b1 in _wino_chunks(n, h, wd, max(c, co)):
                 nb = b1 - b0
                 m, u = _winograd(dya[b0:b1], w, nb, h, wd, co, c, dys is not None, True, st, u=u, key=dya,
@@ -1382,46 +1378,9 @@ def _bwd_side(t: torch.Tensor):
     return side
 
 
-# The Winograd input gradient's filter transform U' (the flipped, transposed filters in the transform domain) depends on
-# the weights alone: it is computed during the forward, on a side stream concurrent with the forward's compute-bound
-# position GEMMs, instead of on the backward's critical path (c4: 31 launches, 4.1 ms per step). The buffers live from
-# the forward to the backward (c4: ~10 GB). Off under graph capture and the bench's instrumented step. Measured neutral
-# (c4 769.1 vs 768.0, c5 976.9 vs 977.0 img/s, same box, interleaved, profiles/r06_ab_winograd_upre.txt: the side-stream
-# transform slows the concurrent GEMMs by about what it hides), so opt-in: MVAE_WINOGRAD_UPRE=1.
-WINOGRAD_UPRE = os.environ.get("MVAE_WINOGRAD_UPRE") is not None
-_UPRE = {}
-
-
-def _upre_launch(w: torch.Tensor, g: ConvGeom, x_shape):
-    """(U' buffer, event) for the conv's Winograd input gradient, launched now on a side stream, or None."""
-    n, c, h, wd = x_shape
-    co = w.shape[0]
-    if not WINOGRAD_UPRE or PROFILE is not None or not w.is_cuda or torch.cuda.is_current_stream_capturing() or \
-            g.upsample or not _wino_ok(g, n, h, wd, co, c) or not _al16(w):
-        return None
-    side = _UPRE.get(w.device)
-    if side is None:
-        side = _UPRE[w.device] = torch.cuda.Stream(w.device)
-    mt = _wtile()
-    u = torch.empty(_wel() * (mt + 2) ** 2 * c * co, dtype=torch.uint8, device=w.device)
-    side.wait_stream(torch.cuda.current_stream(w.device))  # (w as written by the weight prep / optimizer)
-    _lib.call("mvae_winograd_weight_transform", w.data_ptr(), u.data_ptr(), c, co, 1, mt, side.cuda_stream)
-    ev = side.record_event()
-    u.record_stream(side)
-    w.record_stream(side)
-    return u, ev
-
-
-# experiment knob: also overlap the two backward passes of the Winograd convs (their memory-bound transforms against the
-# other pass's GEMM), whatever their size
-BWD_OVERLAP_WINO = os.environ.get("MVAE_BWD_OVERLAP_WINO") is not None
-
-
 def _overlap_ok(x, dy, g) -> bool:
     n, c, h, w = x.shape
     _, co, ho, wo = dy.shape
-    if BWD_OVERLAP_WINO and _wino_ok(g, n, h, w, c, co):
-        return True
     # (image-side convs -- cout 3 / latent channels -- run memory-bound special kernels: c4 lost 0.35 % overlapping them)
     return not g.pointwise and min(c, co) >= 32 and 2.0 * n * ho * wo * co * c * g.kh * g.kw <= BWD_OVERLAP_MAX_FLOPS
 
@@ -1447,7 +1406,6 @@ class Conv2dFn(torch.autograd.Function):
             x = nhwc(x)
         keep = [] if (WINOGRAD_KEEP_V or lazy is not None) and want_w else None
         y = conv2d_forward_raw(x, w, bias, res, geom, xs, gn_part, x_bf16=xb16, keep_v=keep, lazy=lazy)
-        ctx.u_pre = _upre_launch(w, geom, tuple(x.shape)) if (grad_on and ctx.needs_input_grad[0]) else None
         ctx.wino_v = keep if keep else None
         ctx.lazy = lazy  # (the weight gradient re-derives V from it if the kept one is gone: a second backward)
         ctx.math = _MATH[0]  # the backward GEMMs run in the forward's arithmetic
@@ -1484,26 +1442,12 @@ class Conv2dFn(torch.autograd.Function):
         dyb = None
         got = ctx.dypack.take(dy) if ctx.dypack is not None else None
         dys = None
-        if got is not None and ctx.dypack.split == "bias":  # the bias gradient (column sums of dx) by the GroupNorm
-            _, bias_done, db_ret = got
-            if not want_b:
-                db_ret = None
-            elif bias_done:
-                bt = _main_grad(ctx.bias_ref)
-                if bt is not None:
-                    bt.add_(db_ret)
-                    db_ret = None
-        elif got is not None and ctx.dypack.split:  # dy pre-split (and the bias gradient) by the GroupNorm backward
-            dys, bias_done, db_ret = got
-            if not want_b:
-                db_ret = None
-            elif bias_done:
-                bt = _main_grad(ctx.bias_ref)
-                if bt is not None:  # into the flat slot now that dy is known to be the GroupNorm's dx
-                    bt.add_(db_ret)
-                    db_ret = None
-        elif got is not None:  # packed dy (and the bias gradient) from the GroupNorm backward that produced dy
-            dyb, bias_done, db_ret = got
+        if got is not None:  # from the GroupNorm backward that produced dy: the bias gradient (column sums of its dx)
+            taken, bias_done, db_ret = got
+            if not ctx.dypack.split:  # ... with dy packed to bf16
+                dyb = taken
+            elif ctx.dypack.split != "bias":  # ... with dy pre-split ("bias": the bias gradient alone)
+                dys = taken
             if not want_b:
                 db_ret = None
             elif bias_done:
@@ -1576,14 +1520,14 @@ class Conv2dFn(torch.autograd.Function):
                 dx, acc.buf, acc.left = acc.buf, None, acc.n
         elif ctx.needs_input_grad[0]:
             dx = conv2d_dgrad_raw(dy, w, x.shape, g, link if ctx.x_sink is None else None, dys=dys, dyb=dyb,
-                                  dkeep=dkeep, u_pre=ctx.u_pre)
+                                  dkeep=dkeep)
             if ctx.x_sink is not None and ctx.x_sink.park(dx):
                 dx = None
         if side is not None:
             main.wait_event(ev_join)
         elif ctx.needs_input_grad[1]:
             wgrad()
-        ctx.wino_v = dkeep = ctx.u_pre = None  # (released after the join: a later main-stream allocation is ordered after its last use)
+        ctx.wino_v = dkeep = None  # (released after the join: a later main-stream allocation is ordered after its last use)
         if ctx.has_bias and ctx.needs_input_grad[2] and not bias_done:
             tgt = _main_grad(ctx.bias_ref)
             n, co, ho, wo = dy.shape
@@ -1945,20 +1889,6 @@ def _attn_use_fused(q, n: int, c: int) -> bool:
     return _attn_small_ok(q, n, c) and c <= ATTN_FUSED_MAXC
 
 
-# query-block fused attention (csrc/attn_tile.hip) for 64 <= n <= 256 tokens, n % 64 == 0, C % 128 == 0: c4 / c5's
-# 16x16 level (n = 256, C = 1024) and, past ATTN_FUSED_MAXC, the 8x8 mid blocks (n = 64, C = 2048). Forward one launch
-# (scores, softmax and P V in one workgroup per 64 queries; P saved for the backward); backward one launch for dP, dS and
-# dQ plus the two batched GEMMs dV = P^T dO and dK = dS^T Q. Opt-in (MVAE_ATTN_TILE=1): measured at c4's 16x16x1024
-# (tools/attn_bench.py, profiles/r05_attn_bench.txt) it is slower than the unfused path -- fwd 513 vs 366 us, bwd 847 vs
-# 704 us: one 141 KB workgroup per CU walks 96 short K-tiles (12-24 MFMAs per wave each) behind one tile of prefetch, so
-# every K-tile waits on a global load; the batched GEMMs' 256x256 tiles do not
-ATTN_TILE = os.environ.get("MVAE_ATTN_TILE") is not None
-
-
-def _attn_use_tile(q, n: int, c: int) -> bool:
-    return ATTN_TILE and 64 <= n <= 256 and n % 64 == 0 and c % 128 == 0 and _al16(q) and q.shape[0] <= 65535
-
-
 class AttnCoreFn(torch.autograd.Function):
     """softmax(q k^T * C^-1/2, dim=2) v over the h*w tokens of each image (encoder_decoder.py:90-103). n <= 64 (the
     7x7 / 8x8 mid blocks): the fused single-tile kernels, one launch per direction with the scores in LDS and only the
@@ -1985,14 +1915,6 @@ class AttnCoreFn(torch.autograd.Function):
             return o
         ctx.fused = False
         s = torch.empty((b, n, n), device=q.device, dtype=torch.float32)
-        ctx.tile = _attn_use_tile(q, n, c)
-        if ctx.tile:  # S, softmax and P V in one launch; P (s) saved for the backward
-            o = torch.empty_like(q, memory_format=CL)
-            with _timed("attn_gemm", 4.0 * n * n * c * b, (n, c, n, b)):
-                _lib.call("mvae_attention_tile_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                          s.data_ptr(), b, n, c, scale, st)
-            ctx.save_for_backward(q, k, v, s)
-            return o
         _gemm(0, 1, n, n, c, scale, q, c, n * c, k, c, n * c, 0.0, s, n, n * n, b, st)
         _lib.call("mvae_softmax_rows", s.data_ptr(), s.data_ptr(), b * n, n, st)
         o = torch.empty_like(q, memory_format=CL)
@@ -2022,19 +1944,6 @@ class AttnCoreFn(torch.autograd.Function):
             with _timed("attn_gemm", 10.0 * n * n * c * b, (n, c, n, b), 8.0 * n * n * c * b):
                 _lib.call("mvae_attention_small_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
                           p.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), b, n, c, ctx.scale, st)
-            return dq, dk, dv
-        if ctx.tile:
-            if not (do.is_contiguous(memory_format=CL) and _al16(do)):
-                do = do.contiguous(memory_format=CL)
-            dq = torch.empty_like(q, memory_format=CL)
-            ds = torch.empty((b, n, n), device=q.device, dtype=torch.float32)
-            with _timed("attn_gemm", 4.0 * n * n * c * b, (n, c, n, b)):  # dP = dO V^T, dQ = dS K
-                _lib.call("mvae_attention_tile_bwd", k.data_ptr(), v.data_ptr(), do.data_ptr(), p.data_ptr(),
-                          dq.data_ptr(), ds.data_ptr(), b, n, c, ctx.scale, st)
-            dv = torch.empty_like(v, memory_format=CL)
-            _gemm(1, 0, n, c, n, 1.0, p, n, n * n, do, c, n * c, 0.0, dv, c, n * c, b, st)  # dV = P^T dO
-            dk = torch.empty_like(k, memory_format=CL)
-            _gemm(1, 0, n, c, n, 1.0, ds, n, n * n, q, c, n * c, 0.0, dk, c, n * c, b, st)  # dK = dS^T Q (scale in dS)
             return dq, dk, dv
         dp = torch.empty((b, n, n), device=q.device, dtype=torch.float32)
         _gemm(0, 1, n, n, c, 1.0, do, c, n * c, v, c, n * c, 0.0, dp, n, n * n, b, st)   # dP = dO V^T

@@ -232,8 +232,8 @@ def test_conv_default_path_exact(dev, name, fam, monkeypatch):
 def _choose_tile(m, n):
     """The forward / input-gradient tile cost model of csrc/gemm_core.h choose_tile (0 = 256x256, 1 = 256x128),
     restated: the library exports no query for the tile it launches, so this asserts the model, not the launch. It
-    has to follow gemm_core.h:1990-2001 by hand if that model changes, and it does not hold under the experiment
-    knobs MVAE_GEMM_TILE / MVAE_TILE_LEGACY. Should a query be exported, use that instead."""
+    has to follow gemm_core.h:1979-1990 by hand if that model changes, and it does not hold under the experiment
+    knob MVAE_GEMM_TILE. Should a query be exported, use that instead."""
     tm, tn = (256, 256, 128, 128, 64), (256, 128, 256, 128, 64)
     eff, res, area = (1.0, 0.82, 0.82, 0.70, 0.50), (1, 1, 1, 2, 4), (65536, 32768, 32768, 16384, 4096)
     best, bt = 4, 1e300

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Attention core timing at the configs' geometries (c4 / c5 16x16x1024 and mid blocks 8x8x2048, c2 7x7x512, c3
-7x7x128): the fused single-tile kernels (csrc/attn.hip, n <= 64), the query-block fused kernels (csrc/attn_tile.hip,
-64 <= n <= 256) and the unfused path (batched GEMMs around the row softmax), forward and backward, HIP events on the
-launch stream. tools/attn_bench.py [precision]"""
+7x7x128): the fused single-tile kernels (csrc/attn.hip, n <= 64) and the unfused path (batched GEMMs around the row
+softmax), forward and backward, HIP events on the launch stream. tools/attn_bench.py [precision]"""
 import json
 import os
 import sys
@@ -13,7 +12,7 @@ from medvae_disentangled_multimodal_amd import ops  # noqa: E402
 
 SHAPES = [("c4_16x16x1024", 256, 1024, 16), ("c4_8x8x2048", 256, 2048, 8), ("c2_7x7x512", 256, 512, 7),
           ("c3_7x7x128", 512, 128, 7)]
-VARIANTS = {"small": (True, False), "tile": (False, True), "unfused": (False, False)}  # (ATTN_FUSED, ATTN_TILE)
+VARIANTS = {"small": True, "unfused": False}  # ATTN_FUSED
 
 
 def timed(fn, reps=20):
@@ -41,9 +40,9 @@ def main():
         fl_f, fl_b = 4.0 * n * n * c * b, 8.0 * n * n * c * b
         row = {}
         ops.ATTN_FUSED_MAXC = 1 << 30
-        for name, (fused, tile) in VARIANTS.items():
-            ops.ATTN_FUSED, ops.ATTN_TILE = fused, tile
-            if (name == "small" and not ops._attn_small_ok(q, n, c)) or (name == "tile" and not ops._attn_use_tile(q, n, c)):
+        for name, fused in VARIANTS.items():
+            ops.ATTN_FUSED = fused
+            if name == "small" and not ops._attn_small_ok(q, n, c):
                 continue
             qq, kk, vv = (t.detach().requires_grad_() for t in (q, k, v))
             tf = timed(lambda: ops.attention_core(qq, kk, vv))

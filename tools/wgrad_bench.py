@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the conv weight-gradient GEMM (+ its split-K reduce and bias reduce) on c2 / c3 / c4 layer shapes.
-usage: tools/wgrad_bench.py [reps]   (A/B: MVAE_SPLIT_LEGACY=1 in a second process)"""
+usage: tools/wgrad_bench.py [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,4 +32,4 @@ for n, ci, co, h, k in SHAPES:
     tot += us
     fl = 2.0 * n * h * h * co * ci * k * k
     print(f"{(n, ci, co, h, k)}  {us:8.1f} us  {fl / us / 1e6:6.1f} TF/s", flush=True)
-print("legacy" if os.environ.get("MVAE_SPLIT_LEGACY") else "new", f"total {tot:.0f} us")
+print(f"total {tot:.0f} us")
