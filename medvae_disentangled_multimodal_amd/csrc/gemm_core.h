@@ -1856,6 +1856,228 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
   }
 }
 
+// Persistent form of gemm3x_kernel's register-staged loop for the Winograd position GEMMs (pre-split ROW x ROW or
+// COL x COL operands, one split, plain 16-B epilogue: alpha only -- no bias, residual, beta or statistics).
+// The 256-wide tiles hold the whole LDS, one workgroup per CU, so in gemm3x_kernel every tile's cold start (index
+// set-up, first global loads, first LDS fill) and its epilogue run with nothing under them. Here a grid of one
+// workgroup per resident slot walks the tile sequence lin, lin + grid, ... (lin XCD-remapped as in gemm3x_kernel, the
+// sequence position-major, then m, then n: the tiles in flight on one XCD share the position's operand panels) and
+// pipelines across tiles: after the last K-tile of a tile is multiplied the global loads of the next tile's first
+// K-tile are issued into the (free) staging registers, so they land under the epilogue; the epilogue's stores are never waited for, only its LDS staging is fenced by a barrier before the next
+// tile's first LDS fill. One accumulator set, the same 2 x (A + B) LDS images. K-tile order, MFMA sequence and
+// accumulation order per output element are gemm3x_kernel's: the result is bitwise the same.
+template <int BM, int BN, int WGM, int WGN, int AK, int VA, int BKIND, int VB, int PREC>
+__global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs a) {
+  constexpr int NT = 64 * WGM * WGN;
+  constexpr int MF = (MVAE_COL_MF16 && mf_of(AK) == 32) ? 16 : mf_of(AK);
+  static_assert(MF == 16 && (PREC == 0 || PREC == 3), "persistent GEMM: 16x16x32 tiles, 3xBF16 or exact fp32");
+  constexpr int KS = ks_of<MF>(), NR = nr_of<MF>();
+  using acc_t = acc_of<MF>;
+  using LA = Loader<AK, BM, VA, NT, true, PREC>;
+  using LB = Loader<BKIND, BN, VB, NT, false, PREC>;
+  using IA = Img<BM, LA::COL>;
+  using IB = Img<BN, LB::COL>;
+  constexpr int BUF = IA::SIZE + IB::SIZE;
+  constexpr int TM = BM / WGM / MF, TN = BN / WGN / MF;
+  static_assert(TM % 2 == 0, "persistent GEMM: the 16-B epilogue stages half of the wave's rows at a time");
+  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * BUF];
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / WGN, wn = wid - wm * WGN;
+  const int arow = wm * (BM / WGM), brow = wn * (BN / WGN);
+  const int ntile = a.tiles_m * a.tiles_n, total = ntile * a.batch, grid = (int)gridDim.x;
+  int lin = blockIdx.x;
+  if (grid >= 16) {  // XCD-aware remap over the grid (bijective, as gemm3x_kernel's)
+    const int xcd = lin & 7, q = grid >> 3, r = grid & 7;
+    lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+  }
+  // tile l of the sequence -> (m0, n0, batch entry); gemm3x_kernel's orders
+  auto locate = [&](int l, int& m0, int& n0, int& bidx) {
+    bidx = l / ntile;
+    const int tile = l - bidx * ntile;
+    int tm, tn;
+    if (a.xcd_groups > 1 && a.tiles_n > 1) {
+      const int gw = (a.tiles_n + a.xcd_groups - 1) / a.xcd_groups;
+      const int ng = (a.tiles_n + gw - 1) / gw;
+      const int g = min(tile / (a.tiles_m * gw), ng - 1);
+      const int rem = tile - g * a.tiles_m * gw;
+      const int width = g == ng - 1 ? a.tiles_n - g * gw : gw;
+      tm = rem / width;
+      tn = g * gw + (rem - tm * width);
+    } else {
+      tm = tile / a.tiles_n;
+      tn = tile - tm * a.tiles_n;
+    }
+    m0 = tm * BM;
+    n0 = tn * BN;
+  };
+  const int nt = (a.K + BK - 1) / BK;  // K-tiles of every tile (one split, K > 0)
+
+  LA la;
+  LB lb;
+  // first K-tile of tile l -> staging registers
+  auto prefetch = [&](int l) {
+    int m0, n0, bidx;
+    locate(l, m0, n0, bidx);
+    la.init(a, a.A + bidx * a.sA, m0, 0, tid, bidx);
+    lb.init(a, a.B + bidx * a.sB, n0, 0, tid, bidx);
+    la.load(a);
+    lb.load(a);
+  };
+  acc_t acc[TM][TN];
+  auto compute = [&](const __bf16* Ai) {
+    const __bf16* Bi = Ai + IA::SIZE;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      bf16x8 bh[TN], bl[TN];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, ks, lane);
+        bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, ks, lane);
+      }
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const bf16x8 ah = read_frag<BM, LA::COL, MF>(Ai, arow + i * MF, ks, lane);
+        const bf16x8 al = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow + i * MF, ks, lane);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) mma<PREC>(acc[i][j], ah, al, bh[j], bl[j]);
+      }
+    }
+  };
+
+  prefetch(lin);
+  for (int l = lin;;) {
+    // here the staging registers hold the first K-tile of tile l and the LDS is free
+    int m0, n0, bidx;
+    locate(l, m0, n0, bidx);
+    const int lnext = l + grid;
+    const bool more = lnext < total;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) acc[i][j][r] = 0.f;
+    la.store(lds);
+    lb.store(lds + IA::SIZE);
+    if (nt > 1) {
+      la.advance();
+      lb.advance();
+      la.load(a);
+      lb.load(a);
+    }
+    __syncthreads();
+    int t = 0;
+    // steady state: gemm3x_kernel's hand-pipelined K loop (staging of tile t+1 / loads of tile t+2 spread over the
+    // MFMA steps of tile t)
+    constexpr int STEPS = KS * TM;
+    constexpr int NSL = LA::NS + LB::NS;
+#ifndef MVAE_NO_PRIO
+    if (NT >= 512 && wid >= (NT / 64) / 2) __builtin_amdgcn_s_setprio(1);
+#endif
+    for (; t + 2 < nt; ++t) {
+      __bf16* nb = lds + ((t & 1) ^ 1) * BUF;
+      const __bf16* Ai = lds + (t & 1) * BUF;
+      const __bf16* Bi = Ai + IA::SIZE;
+      la.advance();
+      lb.advance();
+      la.prep(a);
+      lb.prep(a);
+      bf16x8 bh[TN], bl[TN], ah[2], al[2];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, 0, lane);
+        bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, 0, lane);
+      }
+      ah[0] = read_frag<BM, LA::COL, MF>(Ai, arow, 0, lane);
+      al[0] = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow, 0, lane);
+      auto stage = [&](int st) {
+#pragma unroll
+        for (int q = st * NSL / STEPS; q < (st + 1) * NSL / STEPS; ++q) {
+          if (q < LA::NS) {
+            la.store_slot(nb, q);
+            la.load_slot(a, q);
+          } else {
+            lb.store_slot(nb + IA::SIZE, q - LA::NS);
+            lb.load_slot(a, q - LA::NS);
+          }
+        }
+      };
+#pragma unroll
+      for (int st = 0; st < STEPS; ++st) {
+        const int i = st % TM, cur = st & 1;
+        if (st + 1 < STEPS) {
+          const int ks1 = (st + 1) / TM, i1 = (st + 1) % TM;
+          ah[cur ^ 1] = read_frag<BM, LA::COL, MF>(Ai, arow + i1 * MF, ks1, lane);
+          al[cur ^ 1] = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow + i1 * MF, ks1, lane);
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) mma<PREC>(acc[i][j], ah[cur], al[cur], bh[j], bl[j]);
+        if (KS == 2 && st == TM - 1) {  // B fragments of the second k-half
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, 1, lane);
+            bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, 1, lane);
+          }
+        }
+        stage(st);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();
+    }
+#ifndef MVAE_NO_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
+    if (t + 1 < nt) {  // last staged K-tile: write it, nothing left to load
+      __bf16* nb = lds + ((t & 1) ^ 1) * BUF;
+      la.store(nb);
+      lb.store(nb + IA::SIZE);
+      compute(lds + (t & 1) * BUF);
+      __syncthreads();
+      ++t;
+    }
+    compute(lds + (t & 1) * BUF);
+    if (more) prefetch(lnext);  // in flight under the epilogue
+
+    // 16-B epilogue through LDS (gemm3x_kernel's vec_epi form): each wave stages half of its accumulator block at a
+    // time as fp32 rows and stores float4 runs of the row; rows / columns outside the matrix are dropped by the
+    // descriptor. The stores stay in flight into the next tile.
+    {
+      constexpr int WR = BM / WGM, WC = BN / WGN, HR = WR / 2, PE = WC + 4;
+      static_assert((NT / 64) * HR * PE * 4 <= 4 * BUF, "epilogue staging exceeds the LDS");
+      constexpr int C4 = WC / 4, RPI = 64 / C4;
+      float* stg = (float*)lds + wid * HR * PE;
+      const __amdgpu_buffer_rsrc_t cr = make_rsrc(a.C + bidx * a.sC, a.c_bytes);
+      const int c4 = lane % C4, rsub = lane / C4;
+      const int col = n0 + brow + c4 * 4;
+      __syncthreads();  // every wave's last fragment reads are done: the LDS is free
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+        for (int i = 0; i < TM / 2; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+              stg[(i * 16 + acc_row<MF>(r, lane)) * PE + j * 16 + (lane & 15)] = acc[pass * (TM / 2) + i][j][r];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < HR / RPI; ++k) {
+          const int lr = k * RPI + rsub;
+          const float4 s4 = *(const float4*)(stg + lr * PE + c4 * 4);
+          const int row = m0 + arow + pass * HR + lr;
+          const bool ok = row < a.M && col < a.N;
+          const unsigned co = ok ? ((unsigned)row * (unsigned)a.ldc + col) * 4u : OOB;
+          bstore4(cr, co, float4{a.alpha * s4.x, a.alpha * s4.y, a.alpha * s4.z, a.alpha * s4.w});
+        }
+        __syncthreads();
+      }
+    }
+    if (!more) break;
+    l = lnext;
+  }
+}
+
 // Fixed-order reduction of split-K partials + the same epilogue.
 __global__ void splitk_reduce_kernel(GemmArgs a);
 // Split-K reduction, 4 columns per thread (N, ldc, ldr multiples of 4; 16-B aligned C / residual / bias): column

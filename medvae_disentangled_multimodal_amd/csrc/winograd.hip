@@ -882,6 +882,47 @@ static int wino_out_launch(WinoOut& p, int tile, bool gnb, void* stream) {
   return launch_status();
 }
 
+// Position GEMMs on the persistent kernel (gemm_core.h gemm3x_persist_kernel): one workgroup per resident slot of the
+// 256 CUs walking the launch's tiles. Taken where the launch spans at least two rounds of the 256-wide tiles in the
+// 3xBF16 or exact-fp32 arithmetic, one split, plain 16-B epilogue; false = not taken (the caller launches
+// gemm3x_kernel). MVAE_NO_PERSISTENT_GEMM (read per call) keeps every launch on gemm3x_kernel: the A/B escape.
+template <int CFG, int AK, int BKIND>
+static bool persist_cfg(GemmArgs& a, hipStream_t st) {
+  constexpr int BM = 256, BN = CFG == T256x256 ? 256 : 128;
+  constexpr int WGM = CFG == T256x128 ? 4 : 2, WGN = CFG == T256x256 ? 4 : 2;
+  a.tiles_m = cdiv(a.M, BM);
+  a.tiles_n = cdiv(a.N, BN);
+  const long long total = (long long)a.tiles_m * a.tiles_n * a.batch, slots = 256LL * resident_of(CFG);
+  if (total <= slots || total > (1LL << 30)) return false;
+  if (a.xcd_groups <= 0) a.xcd_groups = xcd_groups_env();
+  const dim3 grid((unsigned)slots), block(64 * WGM * WGN);
+  if (math_mode() == MATH_FP32) {
+    // (the exact-fp32 256x256 instantiation spills registers to scratch: it stays on gemm3x_kernel)
+    if constexpr (CFG == T256x256) return false;
+    else hipLaunchKernelGGL((gemm3x_persist_kernel<BM, BN, WGM, WGN, AK, 4, BKIND, 4, 0>), grid, block, 0, st, a);
+  } else {
+    hipLaunchKernelGGL((gemm3x_persist_kernel<BM, BN, WGM, WGN, AK, 4, BKIND, 4, 3>), grid, block, 0, st, a);
+  }
+  return true;
+}
+// (forward / input-gradient form only: the weight-gradient COL x COL form compiles through the same kernel but its
+// 256x256 instantiation, the only one that form's launches without split-K use, spills registers to scratch)
+template <int AK, int BKIND>
+static bool launch_persist(GemmArgs& a, hipStream_t st, int cfg) {
+  static_assert(AK == A_ROWK_SPLIT && BKIND == B_ROWK_SPLIT, "persistent GEMM: pre-split ROW x ROW operands");
+#ifdef MVAE_W4  // (a build whose 256x256 tile runs on 4 waves)
+  return false;
+#else
+  if (getenv("MVAE_NO_PERSISTENT_GEMM") != nullptr || math_mode() == MATH_BF16 || a.splits != 1 || a.bias || a.res ||
+      a.beta != 0.f || a.out_remap || a.gn_part || a.gnb_part || a.bias_ws || (a.N & 3) || (a.ldc & 3) || (a.sC & 3) ||
+      !al16(a.C) || vec_epi_disabled())
+    return false;
+  if (cfg == T256x256) return persist_cfg<T256x256, AK, BKIND>(a, st);
+  if (cfg == T256x128) return persist_cfg<T256x128, AK, BKIND>(a, st);
+  return false;
+#endif
+}
+
 }  // namespace mvae
 
 using namespace mvae;
@@ -962,7 +1003,8 @@ int mvae_winograd_gemm(const void* v, const void* u, float* m, long long tiles, 
   set_splits(a, 1);
   auto go = [&](GemmArgs& g, int c) {
     if (pk) conv_dma(A_ROWK, g, (hipStream_t)stream, c, 4);
-    else launch_big<A_ROWK_SPLIT, 4, B_ROWK_SPLIT, 4>(g, (hipStream_t)stream, c);
+    else if (!launch_persist<A_ROWK_SPLIT, B_ROWK_SPLIT>(g, (hipStream_t)stream, c))
+      launch_big<A_ROWK_SPLIT, 4, B_ROWK_SPLIT, 4>(g, (hipStream_t)stream, c);
   };
   const int cfg = choose_tile(a, true, false);
   // wave-quantization tail (as conv2d_impl's): positions whose tiles would leave a nearly empty last round (c2's 7x7x512
