@@ -1060,7 +1060,9 @@ static int gn_resident_slab(int nb, int hw, int C, int G, int* items, int max_it
   const int cpg = C / G;
   for (int sc = std::min(C, GN_RES_MAXC); sc >= 16; sc >>= 1) {
     const int c4 = sc >> 2;
-    if ((c4 & (c4 - 1)) || c4 > GN_RES_NT || C % sc || sc % cpg) continue;
+    // (sc & 3: halving an odd multiple of 4 leaves a slab that is no whole number of channel quads -- C = 1056 at 32
+    // groups reached sc = 66, whose 16 quads cover 64 of the slab's 66 channels)
+    if ((sc & 3) || (c4 & (c4 - 1)) || c4 > GN_RES_NT || C % sc || sc % cpg) continue;
     const int rpar = GN_RES_NT / c4, it = (hw + rpar - 1) / rpar;
     if (it > max_it) continue;
     *items = it <= 4 ? 4 : it <= 8 ? 8 : (it <= 13 && (max_it < 16 || gn_fwd_it13())) ? 13 : 16;  // 13: 28x28 at 32-ch slabs

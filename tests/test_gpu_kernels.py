@@ -411,18 +411,29 @@ def _gn_raw(path, x, gamma, beta, dy, add, groups, silu, drop, seed, y_split=0):
 
 
 # the c3 (28/14/7 at hidden 32) and c2 (hidden 128) levels, whose h*w is not a multiple of 32 (no conv-epilogue
-# statistics): auto selects the register-resident one-pass kernels (backward of larger tensors: the two-pass
-# unit kernel); checked against float64 torch and against the streaming kernels (dropout masks identical: same
-# counter hash)
+# statistics): auto selects the register-resident one-pass kernels; checked against float64 torch and against the
+# streaming kernels (dropout masks identical: same counter hash). The cases of GN_STREAMING_CASES take the streaming
+# chain on both settings (the test asserts which path each case takes; tests/test_gpu_gn_exact.py covers the paths
+# element by element)
+GN_STREAMING_CASES = {(96, 9), (256, 64), (512, 48)}  # (c, h)
 @pytest.mark.parametrize("n,c,h,silu,drop,add", [(3, 32, 28, True, 0.0, True), (3, 64, 14, True, 0.1, False),
                                                   (2, 128, 7, False, 0.0, True), (2, 256, 14, True, 0.0, False),
                                                   (2, 512, 7, True, 0.1, True), (2, 128, 28, True, 0.0, False),
-                                                  (2, 2048, 4, True, 0.0, True), (5, 96, 9, True, 0.0, False),
-                                                  # two-pass unit backward (64x64 / 48x48: too many rows to hold)
+                                                  (2, 2048, 4, True, 0.0, True),
+                                                  # streaming chain: C/4 = 24 is no power of two (no resident slab)
+                                                  (5, 96, 9, True, 0.0, False),
+                                                  # streaming chain: 64x64 / 48x48 are too many rows to hold (the
+                                                  # two-pass unit backward is opt-in, MVAE_GN_UNIT=1, and not run here)
                                                   (2, 256, 64, True, 0.1, True), (2, 512, 48, True, 0.0, False)])
 def test_group_norm_resident_matches_streaming_and_float64(dev, n, c, h, silu, drop, add):
+    import gn_ref
+    from medvae_disentangled_multimodal_amd import _lib
     g = torch.Generator().manual_seed(c * 7 + h)
     G = min(32, c)
+    streaming = (c, h) in GN_STREAMING_CASES
+    assert (gn_ref.fwd_slab(h * h, c, G)[0] == 0) == streaming and (gn_ref.bwd_slab(n, h * h, c, G)[0] == 0) == streaming
+    _lib.call("mvae_set_group_norm_path", 0)
+    assert _lib.query("mvae_group_norm_bwd_streaming", n, h * h, c, G, 0) == int(streaming)
     x = (torch.randn(n, h, h, c, generator=g) * 1.5 + 0.3).to(dev)
     gamma = (1 + 0.2 * torch.randn(c, generator=g)).to(dev)
     beta = (0.1 * torch.randn(c, generator=g)).to(dev)
