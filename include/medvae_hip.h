@@ -483,6 +483,14 @@ int mvae_ssim(const float* x, const float* y, int nb, int h, int w, int c, float
 int mvae_kl_stats(const float* mu, const float* logvar, long long ld, long long npix, int zc, float* out,
                   void* workspace, size_t workspace_bytes, void* stream);
 size_t mvae_kl_stats_workspace_bytes(long long npix);
+/* compute_latent_metrics (src/utils/metrics.py:76-101) on z [batch][pixels][channels] (pixel stride ld >= channels,
+ * image stride stride_image; a [B, D] latent is pixels = 1, channels = D): out = {latent_mean_avg, latent_std_avg
+ * (per-feature unbiased std over the batch, averaged; NaN for batch = 1), latent_sparsity (fraction with |z| < 0.1)}.
+ * 16-byte loads when z, ld, stride_image and channels are multiples of 4 floats, 4-byte loads otherwise; fixed-order
+ * double accumulation, no atomics. */
+int mvae_latent_stats(const float* z, long long ld, long long stride_image, int batch, int pixels, int channels,
+                      float* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t mvae_latent_stats_workspace_bytes(int batch, int pixels, int channels);
 
 /* ---- on-device MedMNIST batches (row (f)1: MedMNISTDataset.__getitem__ + transforms + collate,
  * src/data/medmnist_data.py:16-72,186-251,319-375) ---------------------------------------------------
