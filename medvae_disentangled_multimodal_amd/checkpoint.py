@@ -43,7 +43,12 @@ def lightning_checkpoint(module, epoch: int = 0) -> Dict[str, Any]:
     """The dict `trainer.save_checkpoint` would write for this module: the LightningModule's own state dict
     (`model.*` and the criterion's `criterion.*` -- LPIPS network, discriminator weights and BatchNorm
     buffers), one optimizer state per optimizer (the discriminator's Adam second, lightning_module.py:
-    427-433)."""
+    427-433). Lightning checkpoints at optimisation-step boundaries only: a module inside a gradient-accumulation
+    window (micro-batches in the flat gradient, no step yet) is refused, since the file could not hold that state."""
+    if getattr(module, "accumulating", False):
+        raise RuntimeError("checkpoint: a gradient-accumulation window is open (accumulate_grad_batches = "
+                           f"{module.accumulate_grad_batches}); save at a step boundary, after the window's last "
+                           "fit_step")
     sd = OrderedDict((f"model.{k}", v.detach().contiguous().cpu()) for k, v in module.model.state_dict().items())
     crit = getattr(module, "criterion", None)
     if isinstance(crit, torch.nn.Module):
@@ -71,6 +76,8 @@ def load_checkpoint(module, ckpt, strict: bool = True, load_optimizer: bool = Tr
     if isinstance(ckpt, str):
         ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
     module._graph = None  # a captured step froze the old hyper-parameters (betas / eps / lr) as launch values
+    if hasattr(module, "_reset_window"):
+        module._reset_window()  # (an open accumulation window belongs to the replaced weights: the next fit_step opens one)
     sd = {k[len("model."):]: v for k, v in ckpt["state_dict"].items() if k.startswith("model.")}
     module.model.load_state_dict(sd, strict=strict)
     crit = getattr(module, "criterion", None)

@@ -46,7 +46,12 @@ class DataParallel:
     predecessors), so every rank issues the same sequence of collectives even when ranks use
     different parameters (the disentangled model's per-modality heads). `allreduce_gradients`
     launches whatever never reported (parameters unused this step) and makes the compute stream
-    wait for all collectives before the optimizer."""
+    wait for all collectives before the optimizer.
+
+    Gradient accumulation (accumulate_grad_batches = N): only the window's last micro-batch calls
+    `begin_backward`, so the readiness hooks of the earlier ones are inert (`_armed` is false: no
+    bucket is launched, no collective of any kind) and the last one's buckets carry the whole window's
+    local sum -- as many all-reduces per window as per step at N = 1."""
 
     def __init__(self, module, group=None, bucket_bytes: int = BUCKET_BYTES, overlap: bool = True):
         self.module = module

@@ -10,6 +10,12 @@ The optimizer hooks of the reference -- zero non-finite grads per tensor (on_bef
 run as ONE fused device-side kernel chain (`FusedAdam.step`) over a flat parameter buffer, in that
 order and with the reference's per-tensor semantics. `fit_step` is the whole hot path of one
 Lightning optimisation step: zero_grad -> training_step -> backward -> [all-reduce] -> fused step.
+
+`accumulate_grad_batches = N` (the Trainer flag of the reference's configs) makes fit_step calls micro-batches of a
+window of N: the flat gradient is zeroed and the weight formats are prepared on the window's first micro-batch, every
+backward adds its gradient into the flat slots, and on the window's last micro-batch the exchange runs, the sum is
+divided by N (the gradient of Lightning's loss / N) and non-finite zeroing, clip and Adam/AdamW run once (DESIGN
+section 13).
 """
 from __future__ import annotations
 
@@ -71,12 +77,23 @@ def _zero_side(g):
 class VAELightningModule(_Base):
     def __init__(self, model: nn.Module, optimizer_config: Dict[str, Any], scheduler_config: Dict[str, Any],
                  loss_config: Dict[str, Any], gradient_clip_val: Optional[float] = None,
-                 precision="32", **kwargs):
+                 precision="32", accumulate_grad_batches: int = 1, **kwargs):
         """`precision` stands in for the Lightning Trainer's flag ("32" or "bf16-mixed"): it selects
-        the GEMM arithmetic of the step (ops.set_precision)."""
+        the GEMM arithmetic of the step (ops.set_precision). `accumulate_grad_batches` stands in for the Trainer's
+        flag of that name: fit_step calls are micro-batches, the optimizer steps once per window of that many."""
         super().__init__()
         if precision not in ops._PRECISION:
             raise ValueError(f"precision {precision!r} is not supported on the MI355X path")
+        n = accumulate_grad_batches
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"accumulate_grad_batches must be an int >= 1, got {n!r}")
+        if n > 1 and dict(loss_config).get("type", "vae") == "lpips_discriminator":
+            # (its step is the reference's manual optimisation, which Lightning refuses to combine with accumulation)
+            raise ValueError("accumulate_grad_batches > 1 is not supported with the lpips_discriminator loss "
+                             "(manual optimisation)")
+        self.accumulate_grad_batches = n
+        self._accum_pos = 0  # micro-batches of the open window already in the flat gradient
+        self._presence = None  # modalities seen in the open window (int32 per modality, on the device)
         self.precision = precision
         self.global_step_count = 0
         self.model = model
@@ -91,6 +108,7 @@ class VAELightningModule(_Base):
         self.optimizer: Optional[FusedAdam] = None
         self.scheduler = None
         self.logged: Dict[str, torch.Tensor] = {}
+        self._window_replayed = False  # the open window's first micro-batch was a graph replay (fit_step_graphed)
         self.process_group = None  # set by ddp.DataParallel
         self._usage = None
 
@@ -283,6 +301,17 @@ class VAELightningModule(_Base):
                             "frequency": 1}]
         return [opt]
 
+    @property
+    def accumulating(self) -> bool:
+        """True while a gradient-accumulation window is open (micro-batches in the flat gradient, no step yet)."""
+        return self._accum_pos > 0
+
+    def _reset_window(self):
+        """Forget an open window (an error inside it, a loaded checkpoint): the next fit_step opens a new one."""
+        self._accum_pos = 0
+        self._window_replayed = False
+        ops.flat_weights_stale()
+
     def _used_mask(self) -> Optional[torch.Tensor]:
         if self._kind != "indices" or self._usage is None:
             return None
@@ -290,7 +319,10 @@ class VAELightningModule(_Base):
         if not hasattr(self, "_param_mod"):
             self._param_mod = torch.tensor([self.model.parameter_modality(n) for n in f.names],
                                            dtype=torch.long, device=f.device)
-        present = self.model.modality_presence(self._usage.to(f.device))
+        if self.accumulate_grad_batches > 1 and self._presence is not None:
+            present = self._presence > 0  # a head used by any micro-batch of the window has gradient
+        else:
+            present = self.model.modality_presence(self._usage.to(f.device))
         if self.process_group is not None:
             # a head used on ANY rank receives the averaged gradient on every rank: the mask (clip norm, Adam
             # update and step count) must be the same everywhere or the replicas drift apart
@@ -299,7 +331,8 @@ class VAELightningModule(_Base):
         used = (pm == -1) | ((pm >= 0) & present[pm.clamp_min(0)])
         return used.to(torch.int32)
 
-    def fit_step_graphed(self, batch, batch_idx: int = 0, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def fit_step_graphed(self, batch, batch_idx: int = 0, eps: Optional[torch.Tensor] = None, *,
+                         last_batch: bool = False) -> torch.Tensor:
         """fit_step replayed from captured HIP graphs: the optimisation step (forward, loss, backward, gradient
         exchange, non-finite zeroing, clip, Adam/AdamW) is captured once and then replayed, so the host issues one
         or two graph launches per step instead of ~800 kernel launches (the small 28x28 configs are host-bound
@@ -316,13 +349,23 @@ class VAELightningModule(_Base):
           "split" (any other backend -- gloo cannot be captured -- or MVAE_DP_CAPTURE=split): graph 1 = forward +
                   backward, then the exchange eagerly (synchronous bucketed all-reduce + the per-modality usage OR),
                   graph 2 = the optimizer step reading the exchanged gradients and the usage mask from static
-                  buffers."""
+                  buffers.
+
+        accumulate_grad_batches = N > 1 (with or without data parallelism; "whole" runs as "split"): three captured
+        pieces sharing one pool -- the window's first micro-batch (zero + weight prep + forward + backward), a later
+        micro-batch (forward + backward) and the division by N + optimizer step; at the window's boundary the exchange
+        and the usage mask run eagerly between the last micro-batch's replay and the optimizer's, as in "split". A window is
+        replayed only from its first micro-batch on: one opened eagerly (or met by a re-capture) finishes eagerly,
+        because the later-micro-batch piece reads the weight formats the first piece's replay prepared."""
         if self.use_discriminator:
             raise RuntimeError("fit_step_graphed: adversarial steps run eagerly (fit_step)")
         if self.optimizer is None or self.global_step_count == 0:
             raise RuntimeError("fit_step_graphed: run at least one eager fit_step first")
         ins = list(batch) + ([eps] if eps is not None else [])
         mode = self._dp_capture_mode()
+        nacc = self.accumulate_grad_batches
+        if nacc > 1 and mode == "whole":
+            mode = "split"
         # everything the captured launches freeze as host values: shapes, the optimizer's hyper-parameters
         # (lr, betas, eps, weight decay), clip norm and gradient scale, the GEMM arithmetic, the exchange mode
         opt = self.optimizer
@@ -330,10 +373,12 @@ class VAELightningModule(_Base):
                              for k, v in opt.param_groups[0].items() if k != "params"))
         key = (tuple((tuple(t.shape), t.dtype, t.device) for t in ins), eps is not None, hyper,
                opt.max_grad_norm, getattr(opt, "grad_scale", None), id(opt), id(self.flat), self.precision, mode,
-               id(self.process_group))
+               id(self.process_group), nacc)
         if getattr(self, "_graph_failed", None) == key:  # this step's capture failed before: eager steps
-            return self.fit_step(batch, batch_idx, eps=eps)
+            return self.fit_step(batch, batch_idx, eps=eps, last_batch=last_batch)
         g = getattr(self, "_graph", None)
+        if nacc > 1 and self._accum_pos > 0 and (g is None or g["key"] != key or not self._window_replayed):
+            return self.fit_step(batch, batch_idx, eps=eps, last_batch=last_batch)  # (an eagerly opened window)
         if g is None or g["key"] != key:
             err = None
             try:
@@ -355,10 +400,30 @@ class VAELightningModule(_Base):
                 self._graph = None
                 self._graph_failed = key
                 torch.cuda.synchronize(ins[0].device)
-                return self.fit_step(batch, batch_idx, eps=eps)
+                return self.fit_step(batch, batch_idx, eps=eps, last_batch=last_batch)
         for dst, src in zip(g["inputs"], ins):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
+        if nacc > 1:
+            first, close = self._window_position(last_batch)
+            g["graph" if first else "graph_next"].replay()  # [zero + weight prep +] forward + backward
+            self._window_replayed = True
+            self._accum_pos += 1
+            if close:
+                prev = ops.set_precision(self.precision)
+                try:
+                    if self.process_group is not None:
+                        self.process_group.allreduce_gradients(self.flat)
+                    used = self._used_mask()
+                    if used is not None:
+                        g["used"].copy_(used)
+                finally:
+                    ops.restore_math_mode(prev)
+                g["graph_opt"].replay()
+                self._accum_pos = 0
+                self._window_replayed = False
+                self.global_step_count += 1
+            return g["loss" if first else "loss_next"]
         if mode == "split":
             g["graph"].replay()  # forward + backward
             prev = ops.set_precision(self.precision)
@@ -401,7 +466,27 @@ class VAELightningModule(_Base):
         eps_in = static[nb] if len(static) > nb else None
         rec = dict(inputs=static, salt=salt, key=key, arena=pinned)
         try:
-            if mode != "split":
+            if self.accumulate_grad_batches > 1:
+                graph_next, graph_opt = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                used = torch.ones(len(self.flat.params), dtype=torch.int32, device=dev)
+                prev = ops.set_precision(self.precision)
+                try:
+                    with torch.cuda.graph(graph):
+                        salt.add_(1)
+                        loss = self._forward_backward(static[:nb], batch_idx, eps_in, exchange=False, first=True)
+                    loss, self._last_outputs = loss.detach(), None  # (no autograd graph outlives into the next piece)
+                    # (recorded with the first piece's prepared formats marked fresh, as they are when it replays)
+                    with torch.cuda.graph(graph_next, pool=graph.pool()):
+                        salt.add_(1)
+                        loss_next = self._forward_backward(static[:nb], batch_idx, eps_in, exchange=False, first=False)
+                    with torch.cuda.graph(graph_opt, pool=graph.pool()):
+                        self._close_window(exchange=False)  # (the division by N; the exchange ran eagerly before)
+                        self._optimizer_phase(used=used if self._kind == "indices" else None, exchange=False)
+                finally:
+                    ops.flat_weights_stale()
+                    ops.restore_math_mode(prev)
+                rec.update(graph_next=graph_next, graph_opt=graph_opt, used=used, loss_next=loss_next.detach())
+            elif mode != "split":
                 with torch.cuda.graph(graph):  # recorded, not executed: capturing performs no optimisation step
                     salt.add_(1)
                     loss = self.fit_step(static[:nb], batch_idx, eps=eps_in)
@@ -470,27 +555,53 @@ class VAELightningModule(_Base):
         self.global_step_count += 2
         return loss_g
 
-    def _forward_backward(self, batch, batch_idx, eps, exchange: bool = True) -> torch.Tensor:
+    def _forward_backward(self, batch, batch_idx, eps, exchange: bool = True, first: bool = True) -> torch.Tensor:
         """fit_step's first phase: gradients of this rank's batch in the flat buffer (exchange: the data-parallel
-        bucket all-reduces launched from the backward's readiness hooks)."""
+        bucket all-reduces launched from the backward's readiness hooks). first: the first micro-batch of an
+        accumulation window -- only it zeroes the flat gradient and prepares the weight formats; a later one adds its
+        gradient to the slots and reads the formats prepared for the first (the parameters do not change inside a
+        window). The undivided loss is backpropagated and returned: the window's 1 / accumulate_grad_batches is applied
+        once, to the accumulated gradient (_close_window)."""
         self.model.train()
-        side = _zero_side(self.flat.grad)
+        side = _zero_side(self.flat.grad) if first else None
         if side is not None:
             # the flat gradient is zeroed on a side stream, concurrent with the forward (which never touches it), and
             # joined before the backward's first gradient write
             side.wait_stream(torch.cuda.current_stream(self.flat.grad.device))
             with torch.cuda.stream(side):
                 self.optimizer.zero_grad()
-        else:
+        elif first:
             self.optimizer.zero_grad()
-        ops.prep_flat_weights(self.flat.data)  # every conv weight in the GEMM format, one launch
+        if first:
+            ops.prep_flat_weights(self.flat.data)  # every conv weight in the GEMM format, one launch
         loss = self.training_step(batch, batch_idx, eps=eps)
         if side is not None:
             torch.cuda.current_stream(self.flat.grad.device).wait_stream(side)
+        n = self.accumulate_grad_batches
+        if n > 1 and self._kind == "indices" and self._usage is not None:
+            # the window's modalities: integer OR on the device, read once at the boundary (_used_mask)
+            seen = self.model.modality_presence(self._usage.to(self.flat.device)).to(torch.int32)
+            if self._presence is None or self._presence.shape != seen.shape:
+                self._presence = torch.zeros_like(seen)
+            if first:
+                self._presence.copy_(seen)
+            else:
+                self._presence.bitwise_or_(seen)
         if exchange and self.process_group is not None:
             self.process_group.begin_backward()
         loss.backward()
         return loss
+
+    def _close_window(self, exchange: bool = True):
+        """The boundary of an accumulation window of N > 1: finish the gradient exchange, then divide the accumulated
+        flat gradient by N -- sum_i g_i / N, the gradient of Lightning's sum_i loss_i / N. One correctly rounded division
+        per element instead of a 1 / N loss scale in every backward: each micro-batch's backward is then the one it
+        runs alone (bitwise, in either arithmetic), where (loss / N).backward() re-rounds every bf16 / 3xBF16 operand of
+        the backward for an N that is no power of two; for a power of two the two are the same numbers. Not folded into
+        FusedAdam.grad_scale (the clip norm's arithmetic and the N = 1 launches stay as they are)."""
+        if exchange and self.process_group is not None:
+            self.process_group.allreduce_gradients(self.flat)
+        self.flat.grad.div_(self.accumulate_grad_batches)
 
     def _optimizer_phase(self, used: Optional[torch.Tensor] = None, exchange: bool = True):
         """fit_step's second phase: finish the gradient exchange, then the fused optimizer step (used: the usage mask
@@ -500,9 +611,19 @@ class VAELightningModule(_Base):
         ops.flat_weights_stale()
         self.optimizer.step(used=self._used_mask() if used is None else used)
 
-    def fit_step(self, batch, batch_idx: int = 0, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One optimisation step of Lightning's loop, fused (automatic optimisation, or the
-        reference's manual generator/discriminator pair once the discriminator is active)."""
+    def _window_position(self, last_batch: bool) -> Tuple[bool, bool]:
+        """(first, close) of the micro-batch about to run: it opens the window, it closes it (the window's
+        accumulate_grad_batches-th micro-batch, or one flagged as the epoch's last). The position is this module's own
+        count of fit_step calls, not batch_idx (callers may pass a constant)."""
+        return self._accum_pos == 0, bool(last_batch) or self._accum_pos + 1 >= self.accumulate_grad_batches
+
+    def fit_step(self, batch, batch_idx: int = 0, eps: Optional[torch.Tensor] = None, *,
+                 last_batch: bool = False) -> torch.Tensor:
+        """One micro-batch of Lightning's loop, fused (automatic optimisation, or the reference's manual
+        generator/discriminator pair once the discriminator is active). With accumulate_grad_batches = 1 every call is
+        a whole optimisation step; with N > 1 the optimizer steps on every N-th call, or on a call flagged last_batch
+        (the epoch's last micro-batch closes the window early; its gradient is still divided by N, as in Lightning).
+        Returns the undivided loss, detached."""
         if self.optimizer is None:
             self.configure_optimizers()
         if self.use_discriminator and self.global_step_count >= self.criterion.discriminator_iter_start:
@@ -512,14 +633,29 @@ class VAELightningModule(_Base):
             finally:
                 ops.restore_math_mode(prev)
         self.model.train()
+        first, close = self._window_position(last_batch)
         prev = ops.set_precision(self.precision)
         try:
-            loss = self._forward_backward(batch, batch_idx, eps)
-            self._optimizer_phase()
+            # (a micro-batch that does not close the window exchanges nothing: no begin_backward, so the readiness
+            # hooks stay inert; the closing one's bucket all-reduces carry the whole window's local sum)
+            loss = self._forward_backward(batch, batch_idx, eps, exchange=close, first=first)
+            self._accum_pos += 1
+            if close and self.accumulate_grad_batches > 1:
+                self._close_window()
+                self._optimizer_phase(exchange=False)
+            elif close:
+                self._optimizer_phase()
+        except BaseException:
+            self._reset_window()
+            raise
         finally:
-            ops.flat_weights_stale()
+            # the prepared weight formats outlive a micro-batch that leaves the window open (the parameters have not
+            # changed); the optimizer phase marks them stale
             ops.restore_math_mode(prev)
-        self.global_step_count += 1
+        if close:
+            self._accum_pos = 0
+            self._window_replayed = False
+            self.global_step_count += 1
         # hand back values, not the step's autograd graph: a graph kept alive past the step pins its AccumulateGrad
         # nodes to this step's stream, which breaks the capture of the next step (fit_step_graphed)
         if isinstance(self._last_outputs, dict):
