@@ -14,7 +14,7 @@ import math
 import os
 import weakref
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -221,7 +221,7 @@ DY_SPLIT_MIN = 1 << 18  # elements: below this the extra launch outweighs the st
 
 
 def _al16(*ts) -> bool:
-    return all(t.data_ptr() % 16 == 0 for t in ts)
+    return all(t is None or t.data_ptr() % 16 == 0 for t in ts)
 
 
 # Winograd F(2x2, 3x3) for the 3x3 / stride-1 / pad-1 convs of the wide, low-resolution levels (c4 / c5's 8x8 x 2048 and
@@ -326,15 +326,6 @@ def _wino_ups_ok(g, n: int, h: int, wd: int, cin: int, cout: int) -> bool:
             4 * n * h * wd * cout * 4 <= _MAX_DESC_BYTES)
 
 
-def _lazy_wino(lazy, x, w, b, res, g, gn_part, wgrad: bool) -> bool:
-    """A deferred GroupNorm output can stay deferred: its conv runs the Winograd forward (normalizing on load) and, when
-    the weight gradient is wanted, the Winograd weight gradient on the kept input transform."""
-    n, c, h, wd = x.shape
-    return (_wino_ok(g, n, h, wd, c, w.shape[0]) and _al16(w, lazy.x) and (b is None or _al16(b)) and
-            (res is None or _al16(res)) and (gn_part is None or _wino_blocks(h, wd)) and
-            (not wgrad or WINOGRAD_WGRAD))
-
-
 WINOGRAD_MAX_CHUNKS = 4
 
 
@@ -427,12 +418,6 @@ _DEFERRED_META = {torch.Tensor.shape.__get__, torch.Tensor.size, torch.Tensor.di
                   torch.Tensor.__hash__, torch.Tensor.element_size, torch.Tensor.get_device}
 
 
-def _wino_ups_wgrad_ok(g, x, dy, dw) -> bool:
-    n, c, h, wd = x.shape
-    return (WINOGRAD_WGRAD and _wino_ups_ok(g, n, h, wd, c, dy.shape[1]) and _al16(x, dy, dw) and
-            dy.is_contiguous(memory_format=CL) and dw.is_contiguous(memory_format=CL))
-
-
 def _wino_wgrad_ok(g, x, dy, dw, dys) -> bool:
     n, c, h, wd = x.shape
     co = dy.shape[1]
@@ -457,11 +442,10 @@ def _winograd(src, w, n: int, h: int, wd: int, k_in: int, n_out: int, src_split:
     mt = _wtile()
     t = _wino_tiles(n, h, wd)
     pos = (mt + 2) ** 2
-    dev = src.device
+    dev, kt = src.device, src if key is None else key
     if keep is not None:
         v = torch.empty(_wel() * pos * t * k_in, dtype=torch.uint8, device=dev)
-        kt = src if key is None else key
-        keep.append((v, mt, kt.data_ptr(), kt._version, tuple(chunk)))
+        keep.append(_Kept(v, mt, kt.data_ptr(), kt._version, tuple(chunk)))
     else:
         v = ARENA.get("wino_v", _wel() * pos * t * k_in, dev)
     m = ARENA.get("wino_m", 4 * pos * t * n_out, dev)
@@ -471,8 +455,7 @@ def _winograd(src, w, n: int, h: int, wd: int, k_in: int, n_out: int, src_split:
         _lib.call("mvae_winograd_weight_transform", w.data_ptr(), u.data_ptr(), cin, cout, int(dgrad), mt, st)
     if dkeep is not None:
         d = torch.empty(_wel() * pos * t * k_in, dtype=torch.uint8, device=dev)
-        kt = src if key is None else key
-        dkeep.append((d, mt, kt.data_ptr(), kt._version, tuple(chunk)))
+        dkeep.append(_Kept(d, mt, kt.data_ptr(), kt._version, tuple(chunk)))
         _lib.call("mvae_winograd_dy_transforms", src.data_ptr(), v.data_ptr(), d.data_ptr(), n, h, wd, k_in,
                   int(src_split), mt, st)
     elif gn is not None:
@@ -506,10 +489,6 @@ def _dma_fmt() -> int:
     if _MATH[0] == 0 and PLANAR_DMA:
         return 3
     return 0
-
-
-def _bf16_dma() -> bool:
-    return _dma_fmt() != 0
 
 
 # 3xBF16 mode: the planar DMA path for convolutions of at least this many MACs (the c4 layers; the small layers of the
@@ -801,128 +780,277 @@ def _conv_call(x, w, b, res, y, n, h, wd, c, co, kh, kw, stride, pad_t, pad_l, h
                   mode, st)
 
 
+def _stride2_classes(g, h: int, wd: int) -> bool:
+    """Downsample's input gradient by dx parity class (mvae_conv2d_dgrad_stride2_nhwc): only the useful taps."""
+    return g.stride == 2 and h % 2 == 0 and wd % 2 == 0 and g.kh <= 4 and g.kw <= 4 and STRIDE2_CLASSES
+
+
+@dataclass(frozen=True)
+class ConvPlan:
+    """The kernel path of one conv, decided once (plan_conv) from integers, the math mode and the module's switches.
+    fwd / dgrad / wgrad list the pass's kernel families in dispatch order ("Conv dispatch"): the first is
+    the planned family, the rest what the actual tensors demote it to (_fwd_family / _dgrad_family / _wgrad_family)."""
+    g: ConvGeom
+    n: int
+    c: int
+    h: int
+    w: int
+    co: int
+    math: int
+    shape: tuple          # (_timed's problem tuple)
+    wino: Optional[str]   # "wino" / "wino_ups" when the conv is planned on a Winograd form
+    fwd: Tuple[str, ...]
+    dgrad: Tuple[str, ...]
+    wgrad: Tuple[str, ...]
+    tile: int      # Winograd: output tile m, bytes per transformed element, image chunks ((b0, b1), ...) of one 4 GiB
+    elsize: int    # buffer descriptor each (() off Winograd), and whether the output transform has its 32-pixel blocks
+    chunks: tuple
+    blocks: bool
+    ref: float     # the reference conv's FLOPs (each pass); alg(family): those of the family's algorithm
+    dy_format: Optional[str]  # dy from a producing GroupNorm (DyPack): "packed" bf16, "split" 3xBF16, "bias" (dy read
+    dy_bias: bool             # in fp32: the bias gradient only), None; dy_bias: a producer may send "bias" alone
+    dy_copy_ok: bool  # every backward family reads the packed / split copy, never the fp32 dy
+    dy_pack: bool     # the conv backward packs dy itself for its GEMMs (pack_dy)
+    gn_on_load: bool  # the forward can normalize a GroupNorm input on load and the weight gradient never reads x
+
+    def alg(self, family: str) -> float:
+        if family in ("wino", "wino_ups"):
+            return self.ref * (self.tile + 2) ** 2 / (9.0 * self.tile * self.tile)
+        if family in ("subpixel", "upsample"):
+            return self.ref * 4 / 9
+        return self.ref
+
+
+
+def plan_conv(g: ConvGeom, n: int, c: int, h: int, w: int, cout: int, math_mode: int) -> ConvPlan:
+    """The plan of the conv g on [n, c, h, w] -> cout channels in GEMM arithmetic math_mode. Host integers only: no
+    tensor, no device. Every switch is read here, at call time."""
+    co, math = cout, int(math_mode)
+    prev, _MATH[0] = _MATH[0], math  # (the rule helpers read the current arithmetic: host state only)
+    try:
+        ho, wo = g.out_hw(h, w)
+        taps = g.kh * g.kw
+        macs = float(n) * ho * wo * co * c * taps
+        sub = _subpixel_upsample(g)
+        s1p1 = g.kh == 3 and g.kw == 3 and g.stride == 1 and not g.upsample and \
+            (g.pad_t, g.pad_l, g.pad_b, g.pad_r) == (1, 1, 1, 1)
+        wino = "wino_ups" if _wino_ups_ok(g, n, h, w, c, co) else "wino" if _wino_ok(g, n, h, w, c, co) else None
+        dma = _dma_ok(macs) and not g.pointwise and taps <= 32
+        direct32 = _direct32(g, c, co, w)
+        # dy from a producing GroupNorm. A Winograd conv splits / rounds dy in its own transform: it reads dy in fp32 and
+        # takes the bias gradient only (WINOGRAD_DY_FP32; else the 3xBF16 split, in the bf16-mixed mode too, never packed)
+        wino_fp32_dy = WINOGRAD_DY_FP32 and wino == "wino"
+        dy_bias = bool(DYBIAS and co % 4 == 0 and ((math == 2 and wino == "wino") or wino_fp32_dy or wino == "wino_ups"))
+        dy_format, copy_ok = "bias" if dy_bias else None, False
+        if DYPACK and _dma_fmt() == 2 and wino != "wino" and not g.pointwise and co % 8 == 0 and taps <= 32:
+            # (GroupNorm-partials epilogues and odd channel counts fall back to kernels that read the fp32 dy)
+            dy_format, copy_ok = "packed", not GN_BWD_FUSED and c % 8 == 0 and not g.upsample
+        elif DYSPLIT and ((_dma_fmt() == 0 and math == 0) or (math == 1 and wino == "wino")) and not wino_fp32_dy and \
+                not g.pointwise and not sub and co % 4 == 0 and taps <= 32 and macs >= DYSPLIT_MIN_MACS:
+            dy_format, copy_ok = "split", not GN_BWD_FUSED  # (the 3xBF16 GEMMs and Winograd transforms read the split copy)
+        dy_pack = dma and co % 8 == 0 and wino is None  # (no producer: the conv backward packs dy itself, pack_dy)
+        packed_dy = dy_pack or dy_format == "packed"     # (a Winograd conv's dy never comes packed)
+        pw, ups = g.pointwise, g.upsample
+        def families(*rows):
+            return tuple(f for f, on in rows if on)
+        # each pass in dispatch order. Forward: the Winograd form first (in the bf16-mixed mode it takes the small wide
+        # levels off the LDS-DMA path). Weight gradient: the kernels that read x once ahead of the Winograd and GEMM forms
+        fwd = families((wino, wino), ("dma", dma and c % 8 == 0 and (sub or not ups)), ("pointwise", pw), ("subpixel", sub),
+                       ("direct32", direct32), ("gemm", not pw and not sub))
+        dgrad = families(("wino_ups", wino == "wino_ups"), ("dma", packed_dy), ("wino", wino == "wino"),
+                         ("gnbwd", GN_BWD_FUSED and not pw and not ups and g.stride == 1 and co % 4 == 0),
+                         ("pointwise", pw), ("upsample", ups), ("direct32", direct32),
+                         ("stride2", not ups and _stride2_classes(g, h, w)), ("gemm", not pw and not ups))
+        wgrad = families(("dma", packed_dy and c % 8 == 0 and not ups), ("pointwise", pw),
+                         ("small_cout", SMALL_COUT_WGRAD and co <= 4 and c % 4 == 0 and s1p1),
+                         ("direct", DIRECT_WGRAD and c in (32, 64) and co in DIRECT_WGRAD_COUT and math != 2 and s1p1),
+                         ("wino_ups", WINOGRAD_WGRAD and wino == "wino_ups"), ("subpixel", sub),
+                         ("wino", WINOGRAD_WGRAD and wino == "wino"), ("gemm", True))
+        chunks = tuple(_wino_chunks(n, h, w, max(c, 4 * co if wino == "wino_ups" else co))) if wino else ()
+        return ConvPlan(g, n, c, h, w, co, math, (n, c, h, w, co, g.kh, g.stride, ups), wino, fwd, dgrad, wgrad, _wtile(), _wel(), chunks, _wino_blocks(h, w),
+                        2.0 * macs, dy_format, dy_bias, copy_ok, dy_pack,
+                        bool(WINOGRAD_GN and WINOGRAD_WGRAD and wino == "wino"))
+    finally:
+        _MATH[0] = prev
+
+
+def _fwd_family(p: ConvPlan, x, w, b, res, x_split, x_bf16, gn_part, lazy) -> str:
+    """The forward family of these tensors: the first of p.fwd whose operand conditions hold."""
+    for f in p.fwd:
+        if f == "wino_ups" and (x_bf16 or x_split or lazy is not None or res is not None or gn_part is not None or
+                                not _al16(x, w, b)):
+            continue
+        if f == "wino" and (x_bf16 or not _al16(w, b, res, lazy.x if lazy is not None else x) or
+                            (gn_part is not None and not p.blocks)):
+            continue
+        if f == "dma" and (x_split or lazy is not None or not _al16(x)):
+            continue
+        if f == "direct32" and (gn_part is not None or not _al16(x, w, res)):
+            continue
+        return f
+
+
+def _dgrad_family(p: ConvPlan, dy, w, dx, gn_link, dys, dyb) -> str:
+    """The input-gradient family: dys / dyb are dy pre-split / packed (None: not given), gn_link a GnBwdLink."""
+    link = gn_link is not None and gn_link.usable(dx)
+    cl, dya = dy.is_contiguous(memory_format=CL), dy if dys is None else dys
+    for f in p.dgrad:
+        if f == "wino_ups" and (dyb is not None or dys is not None or not cl or not _al16(dy, w)):
+            continue
+        if f == "dma" and (dyb is None or link):
+            continue
+        if f == "wino" and not (cl and _al16(dya, w)):
+            continue
+        if f == "gnbwd" and not (link and _al16(dy, dx)):
+            continue
+        if f == "direct32" and not _al16(w, dya):
+            continue
+        return f
+
+
+def _wgrad_wino_on(p: ConvPlan) -> bool:
+    """The planned Winograd weight gradient, unless it was switched off after the forward that made the plan."""
+    return WINOGRAD_WGRAD and ("wino" in p.wgrad or "wino_ups" in p.wgrad)
+
+
+def _wgrad_family(p: ConvPlan, x, dy, dw, db, x_split, dys, dyb, lazy) -> str:
+    """The weight-gradient family. Only the Winograd form takes a deferred GroupNorm output (no values to read)."""
+    deferred = isinstance(x, DeferredGnOutput)
+    cl = dy.is_contiguous(memory_format=CL) and dw.is_contiguous(memory_format=CL)
+    for f in p.wgrad:
+        if f == "dma" and (dyb is None or x_split or not _al16(x)):
+            continue
+        if f == "pointwise" and db is not None:
+            continue
+        if f in ("small_cout", "direct", "wino_ups", "subpixel") and deferred:
+            continue
+        if f == "small_cout" and not _al16(x):
+            continue
+        if f == "direct" and (dys is not None or not _al16(x, dy)):
+            continue
+        if f == "wino_ups" and (x_split or not cl or not _al16(x, dy, dw) or not _wgrad_wino_on(p)):
+            continue
+        if f == "wino" and not (cl and _al16(x if lazy is None else lazy.x, dy, dw, dys) and _wgrad_wino_on(p)):
+            continue
+        return f
+
+
+class _Kept(NamedTuple):
+    """A Winograd transform kept between passes: V of the forward's input, D' of the input gradient's dy."""
+    buf: torch.Tensor
+    tile: int
+    src_ptr: int
+    src_version: int
+    chunk: Tuple[int, int]
+
+
+def _kept(entries, tile: int, src) -> dict:
+    """{image chunk: buffer} of the kept transforms of exactly this source tensor (same tile, unchanged since)."""
+    return {e.chunk: e.buf for e in entries or ()
+            if e.tile == tile and e.src_ptr == src.data_ptr() and e.src_version == src._version}
+
+
 def conv2d_forward_raw(x, w, b, res, g: ConvGeom, x_split: bool = False, gn_part=None, x_bf16: bool = False,
-                       keep_v=None, lazy=None):
+                       keep_v=None, lazy=None, plan: Optional[ConvPlan] = None):
     """gn_part (fp64 [n*ho*wo/32 * cout/4 * 2]): also emit the GroupNorm statistics of y from the GEMM
     epilogue (mvae_conv2d_gnstats_nhwc; only on the plain implicit-GEMM path -- the caller checks).
     x_bf16: x holds packed bf16 (BF16_ATTR; bf16-mixed mode)."""
     n, c, h, wd = x.shape
     co = w.shape[0]
+    p = plan if plan is not None else plan_conv(g, n, c, h, wd, co, _MATH[0])
     ho, wo = g.out_hw(h, wd)
     y = torch.empty((n, co, ho, wo), device=x.device, dtype=torch.float32, memory_format=CL)
-    ref = 2.0 * n * ho * wo * co * c * g.kh * g.kw
-    sub = _subpixel_upsample(g)
-    alg = ref * 4 / 9 if sub else ref
     st = _stream(x)
-    # (the vector gather keeps one validity bit per filter tap: kernels of more than 32 taps take the scalar path,
-    # which reads unsplit weights)
-    split = WEIGHT_SPLIT and _splits_ok() and c % 4 == 0 and _al16(x) and not g.pointwise and g.kh * g.kw <= 32
     if x_split and (g.pointwise or g.upsample or c % 4 or not _al16(x)):
         raise RuntimeError("conv2d: a pre-split input needs a non-pointwise, non-upsample conv with cin % 4 == 0")
-    # (the Winograd form first: in the bf16-mixed mode it takes the small wide levels off the LDS-DMA path)
-    wino = not x_bf16 and _wino_ok(g, n, h, wd, c, co) and _al16(w) and (b is None or _al16(b)) and \
-        (res is None or _al16(res)) and (gn_part is None or _wino_blocks(h, wd)) and _al16(lazy.x if lazy is not None else x)
-    wups = not x_bf16 and not x_split and lazy is None and res is None and gn_part is None and \
-        _wino_ups_ok(g, n, h, wd, c, co) and _al16(x, w) and (b is None or _al16(b))
-    if wups:
-        with _timed("conv_fwd", _wino_alg(ref), (n, c, h, wd, co, g.kh, g.stride, g.upsample), ref):
-            kc = ARENA.get("wups_k", 4 * co * 9 * c * 4, x.device)
-            _lib.call("mvae_winograd_upsample_weights", w.data_ptr(), kc.data_ptr(), c, co, st)
-            u = None
-            for b0, b1 in _wino_chunks(n, h, wd, max(c, 4 * co)):
-                m, u = _winograd(x[b0:b1], kc, b1 - b0, h, wd, c, 4 * co, False, False, st, keep_v, key=x, u=u,
-                                 chunk=(b0, b1))
-                _lib.call("mvae_winograd_output_transform_upsample", m.data_ptr(), _ptr(b), y[b0:b1].data_ptr(),
-                          b1 - b0, h, wd, co, _wtile(), st)
-        return y
-    if not wino and _dma_ok(ref / 2) and c % 8 == 0 and not x_split and _al16(x) and not g.pointwise and \
-            g.kh * g.kw <= 32 and (sub or not g.upsample):
-        return _conv_fwd_bf16(x, w, b, res, g, y, n, c, h, wd, co, ho, wo, sub, alg, ref, gn_part, st, x_bf16)
-    if x_bf16:
+    fam = _fwd_family(p, x, w, b, res, x_split, x_bf16, gn_part, lazy)
+    if x_bf16 and fam != "dma":
         raise RuntimeError("conv2d: a packed bf16 input needs the bf16-mixed LDS-DMA conv path")
-    if lazy is not None and not wino:  # a deferred GroupNorm output whose conv cannot normalize on load: write it
+    if lazy is not None and fam != "wino":  # a deferred GroupNorm output whose conv cannot normalize on load: write it
         x, lazy = lazy.materialize(), None
-    if wino:
-        with _timed("conv_fwd", _wino_alg(ref), (n, c, h, wd, co, g.kh, g.stride, g.upsample), ref):
-            src = lazy.x if lazy is not None else x
-            u = None
-            for b0, b1 in _wino_chunks(n, h, wd, max(c, co)):
-                m, u = _winograd(src[b0:b1], w, b1 - b0, h, wd, c, co, x_split, False, st, keep_v, gn=lazy, key=x,
-                                 u=u, chunk=(b0, b1))
+    if fam in ("wino", "wino_ups"):
+        ups = fam == "wino_ups"  # (four class convs on the low-resolution input: N = 4 cout, class-interleaving output)
+        with _timed("conv_fwd", p.alg(fam), p.shape, p.ref):
+            wsrc, src, u = w, lazy.x if lazy is not None else x, None
+            if ups:
+                wsrc = ARENA.get("wups_k", 4 * co * 9 * c * 4, x.device)
+                _lib.call("mvae_winograd_upsample_weights", w.data_ptr(), wsrc.data_ptr(), c, co, st)
+            for b0, b1 in p.chunks:
+                m, u = _winograd(src[b0:b1], wsrc, b1 - b0, h, wd, c, 4 * co if ups else co, x_split, False, st, keep_v,
+                                 gn=lazy, key=x, u=u, chunk=(b0, b1))
+                if ups:
+                    _lib.call("mvae_winograd_output_transform_upsample", m.data_ptr(), _ptr(b), y[b0:b1].data_ptr(),
+                              b1 - b0, h, wd, co, p.tile, st)
+                    continue
                 gp = gn_part[b0 * (h * wd // 32) * (co // 4) * 2:] if gn_part is not None else None
                 _lib.call("mvae_winograd_output_transform", m.data_ptr(), _ptr(b),
                           _ptr(res[b0:b1] if res is not None else None), y[b0:b1].data_ptr(), _ptr(gp), b1 - b0, h,
-                          wd, co, _wtile(), st)
+                          wd, co, p.tile, st)
         return y
-    wg = w
-    if sub:  # tap-summed per-class weights (prepared outside the timed GEMM launch)
-        wg = ARENA.get("w4", 16 * co * c * 4, x.device)
-        _lib.call("mvae_conv_weight_upsample_fwd", w.data_ptr(), wg.data_ptr(), co, c, int(split), st)
-    elif split:
-        wp = _flat_weight_ptr(w, 1)
-        if wp is None:
+    dma = fam == "dma"  # the launches below on packed bf16 (planar) x and weights, staged into LDS by DMA
+    if dma:
+        fam = "subpixel" if g.upsample else "gemm"
+    # (the vector gather keeps one validity bit per filter tap: kernels of more than 32 taps take the scalar path,
+    # which reads unsplit weights)
+    split = not dma and WEIGHT_SPLIT and _splits_ok() and c % 4 == 0 and _al16(x) and not g.pointwise and \
+        g.kh * g.kw <= 32
+    wfmt = _dma_fmt() if dma else int(split)
+    xp = (x if x_bf16 else pack_bf16(x, "xbf")).data_ptr() if dma else x.data_ptr()
+    wptr = w.data_ptr()
+    if fam == "subpixel":  # tap-summed per-class weights (prepared outside the timed GEMM launch)
+        wg = ARENA.get("w4", _dma_bytes(16 * co * c) if dma else 16 * co * c * 4, x.device)
+        _lib.call("mvae_conv_weight_upsample_fwd", w.data_ptr(), wg.data_ptr(), co, c, wfmt, st)
+        wptr = wg.data_ptr()
+    elif dma or split:
+        wptr = _flat_weight_ptr(w, wfmt) if wfmt != 3 else None
+        if wptr is None and dma:
+            wptr = pack_bf16(w, "wsplit").data_ptr()
+        elif wptr is None:
             wg = ARENA.get("wsplit", w.numel() * 4, x.device)
             _lib.call("mvae_split_bf16", w.data_ptr(), wg.data_ptr(), w.numel(), st)
-            wp = wg.data_ptr()
-    wptr = wg.data_ptr() if not split or sub else wp
-    with _timed("conv_fwd", alg, (n, c, h, wd, co, g.kh, g.stride, g.upsample), ref):
-        if g.pointwise:
+            wptr = wg.data_ptr()
+    with _timed("conv_fwd", p.alg(fam), p.shape, p.ref):
+        if fam == "pointwise":
             # 1x1 conv = GEMM [pixels][cin] x [cout][cin]^T
-            _lib.call("mvae_gemm_strided_batched", 0, 1, n * h * wd, co, c, 1.0, x.data_ptr(), c, 0,
-                      w.data_ptr(), c, 0, 0.0, y.data_ptr(), co, 0, 1, _ptr(b), _ptr(res), co, 0, None, 0, st)
-        elif sub:
-            _lib.call("mvae_conv2d_upsample_nhwc", x.data_ptr(), wg.data_ptr(), _ptr(b), _ptr(res), y.data_ptr(), n,
-                      h, wd, c, co, int(split), st)
-        elif gn_part is None and _direct32(g, c, co, wd) and _al16(x, wg) and (res is None or _al16(res)):
-            _lib.call("mvae_conv2d_direct32_nhwc", x.data_ptr(), wptr, _ptr(b), _ptr(res), y.data_ptr(), n, h, wd,
+            _lib.call("mvae_gemm_strided_batched", 0, 1, n * h * wd, co, c, 1.0, xp, c, 0,
+                      wptr, c, 0, 0.0, y.data_ptr(), co, 0, 1, _ptr(b), _ptr(res), co, 0, None, 0, st)
+        elif fam == "subpixel":
+            _lib.call("mvae_conv2d_upsample_nhwc", xp, wptr, _ptr(b), _ptr(res), y.data_ptr(), n, h, wd, c, co, wfmt, st)
+        elif fam == "direct32":
+            _lib.call("mvae_conv2d_direct32_nhwc", xp, wptr, _ptr(b), _ptr(res), y.data_ptr(), n, h, wd,
                       (MVAE_CONV_WSPLIT if split else 0) | (MVAE_CONV_XSPLIT if x_split else 0), st)
         else:
-            mode = (1 if g.upsample else 0) | (MVAE_CONV_WSPLIT if split else 0) | (MVAE_CONV_XSPLIT if x_split else 0)
+            mode = _dma_flag() if dma else \
+                (1 if g.upsample else 0) | (MVAE_CONV_WSPLIT if split else 0) | (MVAE_CONV_XSPLIT if x_split else 0)
             if gn_part is not None:
-                _lib.call("mvae_conv2d_gnstats_nhwc", x.data_ptr(), wptr, _ptr(b), _ptr(res), y.data_ptr(),
+                _lib.call("mvae_conv2d_gnstats_nhwc", xp, wptr, _ptr(b), _ptr(res), y.data_ptr(),
                           n, h, wd, c, co, g.kh, g.kw, g.stride, g.pad_t, g.pad_l, ho, wo, mode, gn_part.data_ptr(), st)
             else:
-                _conv_call(x.data_ptr(), wptr, _ptr(b), _ptr(res), y, n, h, wd, c, co, g.kh, g.kw, g.stride,
-                           g.pad_t, g.pad_l, ho, wo, mode, st)
+                _conv_call(xp, wptr, _ptr(b), _ptr(res), y, n, h, wd, c, co, g.kh, g.kw, g.stride, g.pad_t, g.pad_l,
+                           ho, wo, mode, st)
     return y
 
 
-def _conv_fwd_bf16(x, w, b, res, g, y, n, c, h, wd, co, ho, wo, sub, alg, ref, gn_part, st, x_bf16=False):
-    """bf16-mixed forward on packed bf16 x and weights (MVAE_CONV_BF16)."""
-    fmt, flag = _dma_fmt(), _dma_flag()
-    xb = x if x_bf16 else pack_bf16(x, "xbf")
-    if sub:
-        wg = ARENA.get("w4", _dma_bytes(16 * co * c), x.device)
-        _lib.call("mvae_conv_weight_upsample_fwd", w.data_ptr(), wg.data_ptr(), co, c, fmt, st)
-    else:
-        wp = _flat_weight_ptr(w, 2) if fmt == 2 else None
-        wg = pack_bf16(w, "wsplit") if wp is None else None
-    wptr = wg.data_ptr() if wg is not None else wp
-    with _timed("conv_fwd", alg, (n, c, h, wd, co, g.kh, g.stride, g.upsample), ref):
-        if sub:
-            _lib.call("mvae_conv2d_upsample_nhwc", xb.data_ptr(), wptr, _ptr(b), _ptr(res), y.data_ptr(), n,
-                      h, wd, c, co, fmt, st)
-        elif gn_part is not None:
-            _lib.call("mvae_conv2d_gnstats_nhwc", xb.data_ptr(), wptr, _ptr(b), _ptr(res), y.data_ptr(),
-                      n, h, wd, c, co, g.kh, g.kw, g.stride, g.pad_t, g.pad_l, ho, wo, flag, gn_part.data_ptr(), st)
-        else:
-            _conv_call(xb.data_ptr(), wptr, _ptr(b), _ptr(res), y, n, h, wd, c, co, g.kh, g.kw, g.stride,
-                       g.pad_t, g.pad_l, ho, wo, flag, st)
-    return y
+def _in_hw(g: ConvGeom, ho: int, wo: int) -> Tuple[int, int]:
+    """An input size of g that gives the output (ho, wo): the one there is, at stride 1."""
+    return (ho // 2, wo // 2) if g.upsample else \
+        ((ho - 1) * g.stride + g.kh - g.pad_t - g.pad_b, (wo - 1) * g.stride + g.kw - g.pad_l - g.pad_r)
 
 
-def pack_dy(dy: torch.Tensor, g: ConvGeom, cin: int, bias_out=None, beta: float = 1.0):
-    """dy as packed bf16 for the backward GEMMs of the bf16-mixed mode, or None when that path does not apply.
+def pack_dy(dy: torch.Tensor, g: ConvGeom, cin: int, bias_out=None, beta: float = 1.0, plan: Optional[ConvPlan] = None):
+    """dy as packed bf16 for the backward GEMMs of the bf16-mixed mode, or None when that path does not apply (a
+    Winograd conv reads dy in fp32).
     bias_out: also accumulate the conv bias gradient (beta * bias_out + column sums of the fp32 dy) from the same pass
     (mvae_pack_bf16_colsum). Returns (packed dy or None, whether the bias gradient was produced)."""
-    if not _bf16_dma() or g.pointwise or dy.dim() != 4 or dy.shape[1] % 8 or g.kh * g.kw > 32 or not _al16(dy) or \
-            not dy.is_contiguous(memory_format=CL) or not _dma_ok(float(dy.numel()) * cin * g.kh * g.kw) or \
-            _wino_ok(g, dy.shape[0], dy.shape[2], dy.shape[3], cin, dy.shape[1]) or \
-            _wino_ups_ok(g, dy.shape[0], dy.shape[2] // 2, dy.shape[3] // 2, cin, dy.shape[1]):  # (Winograd: fp32 dy)
+    if dy.dim() != 4 or not _al16(dy) or not dy.is_contiguous(memory_format=CL):
+        return None, False
+    n, co, ho, wo = dy.shape
+    if plan is None:
+        plan = plan_conv(g, n, cin, *_in_hw(g, ho, wo), co, _MATH[0])
+    if not plan.dy_pack:
         return None, False
     if bias_out is None:
         return pack_bf16(dy, "dybf"), False
-    n, co, ho, wo = dy.shape
     rows = n * ho * wo
     out = ARENA.get("dybf", _dma_bytes(dy.numel()), dy.device)
     ws = ARENA.get("bias", _lib.query("mvae_bias_grad_workspace_bytes", rows, co), dy.device)
@@ -943,7 +1071,7 @@ def split_dy(dy: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=None, dkeep=None, out=None,
-                     beta: float = 0.0):
+                     beta: float = 0.0, plan: Optional[ConvPlan] = None):
     """gn_link (GnBwdLink): the conv's input was silu?(GroupNorm(x)) -- also emit that GroupNorm's backward
     partials from the GEMM epilogue (mvae_conv2d_dgrad_gnbwd_nhwc) into gn_link.part when the launch allows it.
     dys: dy pre-split by split_dy (same values; used as the gathered GEMM operand when given).
@@ -953,298 +1081,208 @@ def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=No
     n, c, h, wd = x_shape
     co = w.shape[0]
     _, _, ho, wo = dy.shape
+    p = plan if plan is not None else plan_conv(g, n, c, h, wd, co, _MATH[0])
     if out is not None and not g.pointwise:
         raise RuntimeError("conv2d_dgrad_raw: an accumulating output is for 1x1 convs")
     dx = out if out is not None else torch.empty((n, c, h, wd), device=dy.device, dtype=torch.float32,
                                                  memory_format=CL)
     st = _stream(dy)
-    flops = 2.0 * n * ho * wo * co * c * g.kh * g.kw  # reference count
-    shp = (n, c, h, wd, co, g.kh, g.stride, g.upsample)
-    if dyb is None and dys is None and _wino_ups_ok(g, n, h, wd, c, co) and _al16(dy, w) and \
-            dy.is_contiguous(memory_format=CL):
-        # the Upsample conv's input gradient on the Winograd form: sum over the classes of the class sub-images of dy
-        # convolved with the flipped, transposed class kernels -- one GEMM over K = 4 cout
-        mt = _wtile()
-        pos = (mt + 2) ** 2
-        with _timed("conv_dgrad", _wino_alg(flops), shp, flops):
+    if dys is not None and (g.pointwise or co % 4):
+        dys = None
+    dya = dy if dys is None else dys
+    fam = _dgrad_family(p, dy, w, dx, gn_link, dys, dyb)
+    mt, pos = p.tile, (p.tile + 2) ** 2
+    dma = fam == "dma"  # the launches below on packed bf16 (planar) dy and weights, staged into LDS by DMA
+    if dma:
+        fam, dya = "upsample" if g.upsample else "stride2" if "stride2" in p.dgrad else "gemm", dyb
+    # the dgrad GEMM's K runs over cout: transposed weights [cin][taps][cout], pre-split when cout % 4 == 0
+    split = not dma and WEIGHT_SPLIT and _splits_ok() and \
+        (fam == "gnbwd" or (co % 4 == 0 and _al16(dy) and g.kh * g.kw <= 32))
+    wfmt, wbytes = (_dma_fmt(), _dma_bytes) if dma else (int(split), lambda numel: 4 * numel)
+    # flags of the conv launches (operand formats) and of the gnbwd / stride-2 kernels
+    cflag = _dma_flag() if dma else (MVAE_CONV_WSPLIT if split else 0) | (MVAE_CONV_XSPLIT if dys is not None else 0)
+    kflag = (8 if wfmt == 3 else 4) if dma else int(split) | (2 if dys is not None else 0)
+    if fam == "upsample":
+        wt = ARENA.get("wt", wbytes(c * 16 * co), dy.device)
+        _lib.call("mvae_conv_weight_upsample_dgrad", w.data_ptr(), wt.data_ptr(), co, c, wfmt, st)
+    elif fam in ("gnbwd", "stride2", "gemm"):
+        wtp = _weight_t(w, co, g.kh, g.kw, c, wfmt, wbytes(c * g.kh * g.kw * co), st)
+    with _timed("conv_dgrad", p.alg(fam), p.shape, p.ref):
+        if fam == "wino_ups":
+            # the Upsample conv's input gradient on the Winograd form: sum over the classes of the class sub-images of dy
+            # convolved with the flipped, transposed class kernels -- one GEMM over K = 4 cout
             kc = ARENA.get("wups_k", 4 * co * 9 * c * 4, dy.device)
             _lib.call("mvae_winograd_upsample_weights", w.data_ptr(), kc.data_ptr(), c, co, st)
-            u = ARENA.get("wino_u", _wel() * pos * c * 4 * co, dy.device)
+            u = ARENA.get("wino_u", p.elsize * pos * c * 4 * co, dy.device)
             _lib.call("mvae_winograd_weight_transform", kc.data_ptr(), u.data_ptr(), c, 4 * co, 1, mt, st)
-            for b0, b1 in _wino_chunks(n, h, wd, max(c, 4 * co)):
+            for b0, b1 in p.chunks:
                 nb, t = b1 - b0, _wino_tiles(b1 - b0, h, wd)
-                v = ARENA.get("wino_v", _wel() * pos * t * 4 * co, dy.device)
+                v = ARENA.get("wino_v", p.elsize * pos * t * 4 * co, dy.device)
                 if dkeep is not None:
-                    d = torch.empty(_wel() * pos * t * 4 * co, dtype=torch.uint8, device=dy.device)
-                    dkeep.append((d, mt, dy.data_ptr(), dy._version, (b0, b1)))
+                    d = torch.empty(p.elsize * pos * t * 4 * co, dtype=torch.uint8, device=dy.device)
+                    dkeep.append(_Kept(d, mt, dy.data_ptr(), dy._version, (b0, b1)))
                 else:
-                    d = ARENA.get("wino_d", _wel() * pos * t * 4 * co, dy.device)
+                    d = ARENA.get("wino_d", p.elsize * pos * t * 4 * co, dy.device)
                 _lib.call("mvae_winograd_dy_transforms_upsample", dy[b0:b1].data_ptr(), v.data_ptr(), d.data_ptr(), nb,
                           h, wd, co, mt, st)
                 m = ARENA.get("wino_m", 4 * pos * t * c, dy.device)
                 _lib.call("mvae_winograd_gemm", v.data_ptr(), u.data_ptr(), m.data_ptr(), t, 4 * co, c, mt, st)
                 _lib.call("mvae_winograd_output_transform", m.data_ptr(), None, None, dx[b0:b1].data_ptr(), None, nb, h,
                           wd, c, mt, st)
-        return dx
-    if dyb is not None and (gn_link is None or not gn_link.usable(dx)):
-        return _conv_dgrad_bf16(dyb, w, dx, g, n, c, h, wd, co, ho, wo, flops, shp, st)
-    if dys is not None and (g.pointwise or co % 4):
-        dys = None
-    dya = dy if dys is None else dys
-    if _wino_ok(g, n, h, wd, co, c) and _al16(dya, w) and dy.is_contiguous(memory_format=CL):
-        # the input gradient is the 3x3 / pad-1 conv of dy with the flipped, transposed filters
-        link = gn_link if gn_link is not None and gn_link.usable(dx) and _wino_blocks(h, wd) else None
-        part = torch.empty(n * h * wd // 32 * c * 2, device=dy.device, dtype=torch.float64) if link else None
-        with _timed("conv_dgrad", _wino_alg(flops), shp, flops):
+        elif fam == "wino":
+            # the input gradient is the 3x3 / pad-1 conv of dy with the flipped, transposed filters
+            L = gn_link if gn_link is not None and gn_link.usable(dx) and p.blocks else None
+            part = torch.empty(n * h * wd // 32 * c * 2, device=dy.device, dtype=torch.float64) if L else None
             u = None
-            for b0, b1 in _wino_chunks(n, h, wd, max(c, co)):
+            for b0, b1 in p.chunks:
                 nb = b1 - b0
                 m, u = _winograd(dya[b0:b1], w, nb, h, wd, co, c, dys is not None, True, st, u=u, key=dya,
                                  chunk=(b0, b1), dkeep=dkeep)
-                if link is None:
+                if L is None:
                     _lib.call("mvae_winograd_output_transform", m.data_ptr(), None, None, dx[b0:b1].data_ptr(), None, nb,
-                              h, wd, c, _wtile(), st)
+                              h, wd, c, mt, st)
                 else:  # with the GroupNorm backward partials (mvae_conv2d_dgrad_gnbwd_nhwc's epilogue sums)
-                    L = link
                     _lib.call("mvae_winograd_output_gnbwd", m.data_ptr(), dx[b0:b1].data_ptr(), L.x[b0:b1].data_ptr(),
                               L.mean[b0 * L.groups:].data_ptr(), L.rstd[b0 * L.groups:].data_ptr(),
                               L.gamma.data_ptr(), L.beta.data_ptr(), L.groups, L.silu,
-                              part[b0 * (h * wd // 32) * c * 2:].data_ptr(), nb, h, wd, c, _wtile(), st)
-            if link is not None:
-                link.part, link.dx = part, dx
-        return dx
-    if gn_link is not None and gn_link.usable(dx) and not g.pointwise and not g.upsample and g.stride == 1 and \
-            co % 4 == 0 and _al16(dy, dx):
-        split = WEIGHT_SPLIT and _splits_ok()
-        wtp = _weight_t(w, co, g.kh, g.kw, c, int(split), c * g.kh * g.kw * co * 4, st)
-        part = torch.empty(n * h * wd // 32 * c * 2, device=dy.device, dtype=torch.float64)
-        L = gn_link
-        flags = int(split) | (2 if dys is not None else 0)
-        with _timed("conv_dgrad", flops, shp):
+                              part[b0 * (h * wd // 32) * c * 2:].data_ptr(), nb, h, wd, c, mt, st)
+            if L is not None:
+                L.part, L.dx = part, dx
+        elif fam == "gnbwd":
+            L = gn_link
+            part = torch.empty(n * h * wd // 32 * c * 2, device=dy.device, dtype=torch.float64)
             _lib.call("mvae_conv2d_dgrad_gnbwd_nhwc", dya.data_ptr(), wtp, dx.data_ptr(), n, ho, wo, co, c,
-                      g.kh, g.kw, g.pad_t, g.pad_l, h, wd, flags, L.x.data_ptr(), L.mean.data_ptr(),
+                      g.kh, g.kw, g.pad_t, g.pad_l, h, wd, kflag, L.x.data_ptr(), L.mean.data_ptr(),
                       L.rstd.data_ptr(), L.gamma.data_ptr(), L.beta.data_ptr(), L.groups, L.silu, part.data_ptr(), st)
-        L.part, L.dx = part, dx
-        return dx
-    if g.pointwise:
-        # dx[m][c] = sum_n dy[m][n] W[n][c]  (W stored [K=cout][N=cin])
-        with _timed("conv_dgrad", flops, shp):
+            L.part, L.dx = part, dx
+        elif fam == "pointwise":
+            # dx[m][c] = sum_n dy[m][n] W[n][c]  (W stored [K=cout][N=cin])
             _lib.call("mvae_gemm_strided_batched", 0, 0, n * h * wd, c, co, 1.0, dy.data_ptr(), co, 0, w.data_ptr(), c,
                       0, float(beta), dx.data_ptr(), c, 0, 1, None, None, 0, 0, None, 0, st)
-        return dx
-    # the dgrad GEMM's K runs over cout: transposed weights [cin][taps][cout], pre-split when cout % 4 == 0
-    split = WEIGHT_SPLIT and _splits_ok() and co % 4 == 0 and _al16(dy) and g.kh * g.kw <= 32
-    wflag = MVAE_CONV_WSPLIT if split else 0
-    xflag = MVAE_CONV_XSPLIT if dys is not None else 0
-    if g.upsample:
-        wt = ARENA.get("wt", c * 16 * co * 4, dy.device)
-        _lib.call("mvae_conv_weight_upsample_dgrad", w.data_ptr(), wt.data_ptr(), co, c, int(split), st)
-        # dX = stride-2, pad-1 4x4 conv of dY with the tap-summed kernel (16 taps per low-res pixel)
-        with _timed("conv_dgrad", flops * 4 / 9, shp, flops):
+        elif fam == "upsample":
+            # dX = stride-2, pad-1 4x4 conv of dY with the tap-summed kernel (16 taps per low-res pixel)
             _lib.call("mvae_conv2d_nhwc", dya.data_ptr(), wt.data_ptr(), None, None, dx.data_ptr(), n, ho, wo, co, c,
-                      4, 4, 2, 1, 1, h, wd, wflag | xflag, st)
-        return dx
-    if _direct32(g, c, co, wd) and _al16(w, dya):
-        # 32 -> 32 channels (c3's 28x28 level): the direct stencil kernel with the flipped, transposed taps
-        with _timed("conv_dgrad", flops, shp):
+                      4, 4, 2, 1, 1, h, wd, cflag, st)
+        elif fam == "direct32":
+            # 32 -> 32 channels (c3's 28x28 level): the direct stencil kernel with the flipped, transposed taps
             _lib.call("mvae_conv2d_direct32_nhwc", dya.data_ptr(), w.data_ptr(), None, None, dx.data_ptr(), n, h, wd,
-                      MVAE_CONV_DGRAD_DIRECT | xflag, st)
-        return dx
-    wtp = _weight_t(w, co, g.kh, g.kw, c, int(split), c * g.kh * g.kw * co * 4, st)
-    if g.stride == 2 and h % 2 == 0 and wd % 2 == 0 and g.kh <= 4 and g.kw <= 4 and STRIDE2_CLASSES:
-        # Downsample's input gradient by dx parity class: only the useful taps (no stride holes)
-        wc = ARENA.get("wcls", c * g.kh * g.kw * co * 4, dy.device)
-        flags = int(split) | (2 if dys is not None else 0)
-        with _timed("conv_dgrad", flops, shp):
+                      MVAE_CONV_DGRAD_DIRECT | (MVAE_CONV_XSPLIT if dys is not None else 0), st)
+        elif fam == "stride2":
+            wc = ARENA.get("wcls", c * g.kh * g.kw * co * 4, dy.device)
             _lib.call("mvae_conv2d_dgrad_stride2_nhwc", dya.data_ptr(), wtp, dx.data_ptr(), n, h, wd, c, co,
-                      g.kh, g.kw, g.pad_t, g.pad_l, ho, wo, flags, wc.data_ptr(), wc.numel(), st)
-        return dx
-    with _timed("conv_dgrad", flops, shp):
-        _conv_call(dya.data_ptr(), wtp, None, None, dx, n, ho, wo, co, c, g.kh, g.kw, g.stride, g.pad_t,
-                   g.pad_l, h, wd, 2 | wflag | xflag, st)
-    return dx
-
-
-def _conv_dgrad_bf16(dyb, w, dx, g, n, c, h, wd, co, ho, wo, flops, shp, st):
-    """bf16-mixed input gradient on packed bf16 dy and weights (MVAE_CONV_BF16)."""
-    dev = dx.device
-    fmt, flag = _dma_fmt(), _dma_flag()
-    if g.upsample:
-        wt = ARENA.get("wt", _dma_bytes(c * 16 * co), dev)
-        _lib.call("mvae_conv_weight_upsample_dgrad", w.data_ptr(), wt.data_ptr(), co, c, fmt, st)
-        with _timed("conv_dgrad", flops * 4 / 9, shp, flops):
-            # dX = stride-2, pad-1 4x4 (forward-gather) conv of dY with the tap-summed kernel
-            _lib.call("mvae_conv2d_nhwc", dyb.data_ptr(), wt.data_ptr(), None, None, dx.data_ptr(), n, ho, wo, co, c,
-                      4, 4, 2, 1, 1, h, wd, flag, st)
-        return dx
-    wtp = _weight_t(w, co, g.kh, g.kw, c, fmt, _dma_bytes(c * g.kh * g.kw * co), st)
-    if g.stride == 2 and h % 2 == 0 and wd % 2 == 0 and g.kh <= 4 and g.kw <= 4 and STRIDE2_CLASSES:
-        wc = ARENA.get("wcls", c * g.kh * g.kw * co * 4, dev)
-        with _timed("conv_dgrad", flops, shp):
-            _lib.call("mvae_conv2d_dgrad_stride2_nhwc", dyb.data_ptr(), wtp, dx.data_ptr(), n, h, wd, c, co,
-                      g.kh, g.kw, g.pad_t, g.pad_l, ho, wo, 8 if fmt == 3 else 4, wc.data_ptr(), wc.numel(), st)
-        return dx
-    with _timed("conv_dgrad", flops, shp):
-        _conv_call(dyb.data_ptr(), wtp, None, None, dx, n, ho, wo, co, c, g.kh, g.kw, g.stride, g.pad_t,
-                   g.pad_l, h, wd, 2 | flag, st)
+                      g.kh, g.kw, g.pad_t, g.pad_l, ho, wo, kflag, wc.data_ptr(), wc.numel(), st)
+        else:
+            _conv_call(dya.data_ptr(), wtp, None, None, dx, n, ho, wo, co, c, g.kh, g.kw, g.stride, g.pad_t,
+                       g.pad_l, h, wd, 2 | cflag, st)
     return dx
 
 
 def conv2d_wgrad_raw(dy, x, dw, beta: float, g: ConvGeom, db=None, x_split: bool = False, dys=None, dyb=None,
-                     x_bf16: bool = False, wino_v=None, wino_d=None, lazy=None):
+                     x_bf16: bool = False, wino_v=None, wino_d=None, lazy=None, plan: Optional[ConvPlan] = None):
     """dw (+ db when given and the conv is not pointwise) accumulate with `beta`. Returns True when
     the bias gradient was produced by the fused wgrad kernel. dys: dy pre-split by split_dy; dyb: dy as packed bf16
     (pack_dy, bf16-mixed mode). lazy (LazyGn): x is a deferred GroupNorm output -- the Winograd weight gradient takes
     the forward's kept V (or re-derives it from the GroupNorm input); any other weight gradient gets x written first."""
     n, c, h, wd = x.shape
-    co = dy.shape[1]
-    _, _, ho, wo = dy.shape
-    if lazy is not None and (dyb is not None or not _wino_wgrad_ok(g, lazy.x, dy, dw, dys)):
+    _, co, ho, wo = dy.shape
+    p = plan if plan is not None else plan_conv(g, n, c, h, wd, co, _MATH[0])
+    fam = _wgrad_family(p, x, dy, dw, db, x_split, dys, dyb, lazy)
+    if lazy is not None and fam != "wino":
         x, lazy = lazy.materialize(), None
-    ref = 2.0 * n * ho * wo * co * c * g.kh * g.kw
-    alg = ref * 4 / 9 if _subpixel_upsample(g) else ref
-    if dyb is None and (_wino_wgrad_ok(g, x if lazy is None else lazy.x, dy, dw, dys) or _wino_ups_wgrad_ok(g, x, dy, dw)):
-        alg = _wino_alg(ref)
-    if dyb is not None and not x_split and not g.upsample and c % 8 == 0 and co % 8 == 0 and _al16(x):
-        # bf16-mixed weight gradient on packed bf16 dy and x (LDS-DMA main loop); the bias gradient is summed from the
-        # fp32 dy by the caller
-        xb = x if x_bf16 else pack_bf16(x, "xbf")
-        st = _stream(dy)
-        nbytes = _lib.query("mvae_conv2d_wgrad_workspace_bytes", n, c, co, g.kh, g.kw, ho, wo)
-        ws = ARENA.get("ws", nbytes, dy.device)
-        with _timed("conv_wgrad", alg, (n, c, h, wd, co, g.kh, g.stride, g.upsample), ref):
-            _lib.call("mvae_conv2d_wgrad_nhwc", dyb.data_ptr(), xb.data_ptr(), dw.data_ptr(), None, float(beta), n, h,
-                      wd, c, co, g.kh, g.kw, g.stride, g.pad_t, g.pad_l, ho, wo, _dma_flag(), ws.data_ptr(),
-                      ws.numel(), st)
-        return False
-    if x_bf16:
+        fam = _wgrad_family(p, x, dy, dw, db, x_split, dys, dyb, None)
+    if x_bf16 and fam != "dma":
         raise RuntimeError("conv2d wgrad: a packed bf16 input needs the bf16-mixed LDS-DMA path (packed dy, cout % 8)")
-    with _timed("conv_wgrad", alg, (n, c, h, wd, co, g.kh, g.stride, g.upsample), ref):
-        return _conv_wgrad_launch(dy, x, dw, beta, g, n, c, h, wd, co, ho, wo, db, x_split, dys, wino_v, wino_d, lazy)
-
-
-def _conv_wgrad_launch(dy, x, dw, beta, g, n, c, h, wd, co, ho, wo, db=None, x_split=False, dys=None, wino_v=None,
-                       wino_d=None, lazy=None):
-    st = _stream(dy)
-    # a deferred GroupNorm output has no values to read: its weight gradient is the Winograd one, on the kept (or
-    # re-derived) V, ahead of the kernels below that read x -- the direct cout-32 kernel would otherwise take a 32-channel
-    # conv and read n*h*w*c floats from the placeholder's one-element allocation
-    deferred = isinstance(x, DeferredGnOutput)
-    if deferred and (lazy is None or not _wino_wgrad_ok(g, lazy.x, dy, dw, dys)):
-        # (conv2d_wgrad_raw materializes such an x for every other path: reaching here would read the placeholder)
+    if isinstance(x, DeferredGnOutput) and (lazy is None or fam != "wino"):
         raise RuntimeError("conv2d wgrad: a deferred GroupNorm output reached a weight-gradient kernel that reads x")
     if x_split and (g.pointwise or g.upsample):
         raise RuntimeError("conv2d wgrad: a pre-split input needs a non-pointwise, non-upsample conv")
-    if g.pointwise and db is None:
-        m = n * h * wd
-        nbytes = _lib.query("mvae_gemm_workspace_bytes", co, c, m, 1)
-        ws = ARENA.get("ws", nbytes, dy.device)
-        # dW[n][c] = sum_m dy[m][n] x[m][c]: A = dy stored [K=m][M=cout], B = x stored [K=m][N=cin]
-        _lib.call("mvae_gemm_strided_batched", 1, 0, co, c, m, 1.0, dy.data_ptr(), co, 0, x.data_ptr(), c, 0,
-                  float(beta), dw.data_ptr(), c, 0, 1, None, None, 0, 0, ws.data_ptr(), ws.numel(), st)
-        return False
-    if (not deferred and SMALL_COUT_WGRAD and co <= 4 and c % 4 == 0 and not g.upsample and g.kh == 3 and g.kw == 3 and g.stride == 1
-            and (g.pad_t, g.pad_l, g.pad_b, g.pad_r) == (1, 1, 1, 1) and _al16(x)):
-        # Decoder.conv_out (cout 3): x read once, scattered into its 9 taps (no 9x im2col stream)
-        nbytes = _lib.query("mvae_conv2d_wgrad_small_cout_workspace_bytes", n, c)
-        ws = ARENA.get("ws", nbytes, dy.device)
-        _lib.call("mvae_conv2d_wgrad_small_cout_nhwc", dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db),
-                  float(beta), n, h, wd, c, co, int(x_split), ws.data_ptr(), ws.numel(), st)
+    st, dev = _stream(dy), dy.device
+    mt, pos = p.tile, (p.tile + 2) ** 2
+
+    def ws(query, *args):
+        return ARENA.get("ws", _lib.query(query, *args), dev)
+
+    with _timed("conv_wgrad", p.alg(fam), p.shape, p.ref):
+        if fam == "pointwise":
+            m = n * h * wd
+            s = ws("mvae_gemm_workspace_bytes", co, c, m, 1)
+            # dW[n][c] = sum_m dy[m][n] x[m][c]: A = dy stored [K=m][M=cout], B = x stored [K=m][N=cin]
+            _lib.call("mvae_gemm_strided_batched", 1, 0, co, c, m, 1.0, dy.data_ptr(), co, 0, x.data_ptr(), c, 0,
+                      float(beta), dw.data_ptr(), c, 0, 1, None, None, 0, 0, s.data_ptr(), s.numel(), st)
+            return False
+        if fam in ("small_cout", "direct", "subpixel"):
+            # x read once. small_cout: Decoder.conv_out, x scattered into its 9 taps; direct: cout 32 (c3's 28x28 / 14x14
+            # levels), per-tap MFMA products over LDS row bands (28x28x32 at bs 512: 128 -> 75 us, tools/wgrad_bench.py)
+            fn = {"small_cout": "mvae_conv2d_wgrad_small_cout", "direct": "mvae_conv2d_wgrad_direct",
+                  "subpixel": "mvae_conv2d_wgrad_upsample"}[fam]
+            s = ws(fn + "_workspace_bytes", *((n, c) if fam == "small_cout" else (n, h, wd, c, co)))
+            _lib.call(fn + "_nhwc", dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db), float(beta), n, h, wd, c, co,
+                      *(() if fam == "subpixel" else (int(x_split),)), s.data_ptr(), s.numel(), st)
+            return db is not None
+        if fam == "wino_ups":
+            # the Upsample conv's weight gradient on the Winograd form: the class kernels' gradients
+            # G^T [sum_t D'_pq (.) V] G (D' of the class sub-images of dy, kept by the input gradient's pass; V the
+            # forward's), folded onto the taps
+            kept, kept_d = _kept(wino_v, mt, x), _kept(wino_d, mt, dy)
+            dkc = ARENA.get("wups_dk", 4 * co * 9 * c * 4, dev)
+            for i, (b0, b1) in enumerate(p.chunks):
+                nb, t = b1 - b0, _wino_tiles(b1 - b0, h, wd)
+                v, dt = kept.get((b0, b1)), kept_d.get((b0, b1))
+                if dt is None:
+                    dt = ARENA.get("wino_d", p.elsize * pos * t * 4 * co, dev)
+                    _lib.call("mvae_winograd_dy_transforms_upsample", dy[b0:b1].data_ptr(), None, dt.data_ptr(), nb, h,
+                              wd, co, mt, st)
+                if v is None:
+                    v = ARENA.get("wino_v", p.elsize * pos * t * c, dev)
+                    _lib.call("mvae_winograd_input_transform", x[b0:b1].data_ptr(), v.data_ptr(), nb, h, wd, c, 0, mt,
+                              st)
+                m = ARENA.get("wino_mw", 4 * pos * 4 * co * c, dev)
+                s = ws("mvae_gemm_workspace_bytes", 4 * co, c, t, pos)
+                _lib.call("mvae_winograd_wgrad_gemm", dt.data_ptr(), v.data_ptr(), m.data_ptr(), t, 4 * co, c, mt,
+                          s.data_ptr(), s.numel(), st)
+                _lib.call("mvae_winograd_wgrad_output", m.data_ptr(), dkc.data_ptr(), 0.0 if i == 0 else 1.0, 4 * co, c,
+                          mt, st)
+            _lib.call("mvae_winograd_upsample_fold", dkc.data_ptr(), dw.data_ptr(), float(beta), c, co, st)
+            return False
+        if fam == "wino":
+            # Winograd F(3x3, 2x2): dW = G^T [sum_tiles (A D A^T) (.) (B^T X B)] G (csrc/winograd.hip); the bias gradient
+            # is the caller's. V / D': kept per image chunk by the forward / the input gradient's pass over dy
+            dya = dys if dys is not None else dy
+            kept, kept_d = _kept(wino_v, mt, x), _kept(wino_d, mt, dya)
+            for i, (b0, b1) in enumerate(p.chunks):
+                nb, t = b1 - b0, _wino_tiles(b1 - b0, h, wd)
+                v, dt = kept.get((b0, b1)), kept_d.get((b0, b1))
+                m = ARENA.get("wino_mw", 4 * pos * co * c, dev)
+                s = ws("mvae_gemm_workspace_bytes", co, c, t, pos)
+                if dt is None:
+                    dt = ARENA.get("wino_d", p.elsize * pos * t * co, dev)
+                    _lib.call("mvae_winograd_dy_transform", dya[b0:b1].data_ptr(), dt.data_ptr(), nb, h, wd, co,
+                              int(dys is not None), mt, st)
+                if v is None and lazy is not None:  # (the kept V is gone -- a second backward: re-derived, normalized on load)
+                    v = ARENA.get("wino_v", p.elsize * pos * t * c, dev)
+                    _lib.call("mvae_winograd_input_transform_gn", lazy.x[b0:b1].data_ptr(),
+                              lazy.scale[b0 * c:].data_ptr(), lazy.shift[b0 * c:].data_ptr(), lazy.silu, v.data_ptr(),
+                              nb, h, wd, c, mt, st)
+                elif v is None:
+                    v = ARENA.get("wino_v", p.elsize * pos * t * c, dev)
+                    _lib.call("mvae_winograd_input_transform", x[b0:b1].data_ptr(), v.data_ptr(), nb, h, wd, c,
+                              int(x_split), mt, st)
+                _lib.call("mvae_winograd_wgrad_gemm", dt.data_ptr(), v.data_ptr(), m.data_ptr(), t, co, c, mt,
+                          s.data_ptr(), s.numel(), st)
+                # (image chunks accumulate: the first with the caller's beta, the rest onto it)
+                _lib.call("mvae_winograd_wgrad_output", m.data_ptr(), dw.data_ptr(), float(beta) if i == 0 else 1.0, co,
+                          c, mt, st)
+            return False
+        # the implicit GEMM ("dma": on packed dy and x); a packed / pre-split dy has no in-kernel bias sum (the caller's)
+        dya, xp, mode = dy, x, (1 if g.upsample else 0) | (MVAE_CONV_XSPLIT if x_split else 0)
+        if fam == "dma":
+            dya, xp, mode, db = dyb, x if x_bf16 else pack_bf16(x, "xbf"), _dma_flag(), None
+        elif dys is not None and co % 4 == 0:
+            dya, mode, db = dys, mode | MVAE_CONV_DYSPLIT, None
+        s = ws("mvae_conv2d_wgrad_workspace_bytes", n, c, co, g.kh, g.kw, ho, wo)
+        _lib.call("mvae_conv2d_wgrad_nhwc", dya.data_ptr(), xp.data_ptr(), dw.data_ptr(), _ptr(db), float(beta), n, h, wd,
+                  c, co, g.kh, g.kw, g.stride, g.pad_t, g.pad_l, ho, wo, mode, s.data_ptr(), s.numel(), st)
         return db is not None
-    if (not deferred and DIRECT_WGRAD and dys is None and c in (32, 64) and co in DIRECT_WGRAD_COUT and _MATH[0] != 2 and
-            not g.upsample and g.kh == 3 and g.kw == 3 and g.stride == 1 and (g.pad_t, g.pad_l, g.pad_b, g.pad_r) == (1, 1, 1, 1) and
-            _al16(x, dy)):
-        # cout 32 (c3's 28x28 / 14x14 levels): per-tap MFMA products over LDS-resident row bands; 28x28x32 at bs 512
-        # 128 -> 75 us, 28x28 64->32 185 -> 118 us (tools/wgrad_bench.py); cout 64 ties the GEMM and keeps it
-        nbytes = _lib.query("mvae_conv2d_wgrad_direct_workspace_bytes", n, h, wd, c, co)
-        ws = ARENA.get("ws", nbytes, dy.device)
-        _lib.call("mvae_conv2d_wgrad_direct_nhwc", dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db), float(beta),
-                  n, h, wd, c, co, int(x_split), ws.data_ptr(), ws.numel(), st)
-        return db is not None
-    if not deferred and not x_split and _wino_ups_wgrad_ok(g, x, dy, dw):
-        # the Upsample conv's weight gradient on the Winograd form: the class kernels' gradients G^T [sum_t D'_pq (.) V] G
-        # (D' of the class sub-images of dy, kept by the input gradient's pass; V the forward's), folded onto the taps
-        mt = _wtile()
-        pos = (mt + 2) ** 2
-        dev = dy.device
-        kept = {e[4]: e[0] for e in wino_v or () if e[1] == mt and e[2] == x.data_ptr() and e[3] == x._version}
-        kept_d = {e[4]: e[0] for e in wino_d or () if e[1] == mt and e[2] == dy.data_ptr() and e[3] == dy._version}
-        dkc = ARENA.get("wups_dk", 4 * co * 9 * c * 4, dev)
-        for i, (b0, b1) in enumerate(_wino_chunks(n, h, wd, max(c, 4 * co))):
-            nb, t = b1 - b0, _wino_tiles(b1 - b0, h, wd)
-            v, dt = kept.get((b0, b1)), kept_d.get((b0, b1))
-            if dt is None:
-                dt = ARENA.get("wino_d", _wel() * pos * t * 4 * co, dev)
-                _lib.call("mvae_winograd_dy_transforms_upsample", dy[b0:b1].data_ptr(), None, dt.data_ptr(), nb, h, wd,
-                          co, mt, st)
-            if v is None:
-                v = ARENA.get("wino_v", _wel() * pos * t * c, dev)
-                _lib.call("mvae_winograd_input_transform", x[b0:b1].data_ptr(), v.data_ptr(), nb, h, wd, c, 0, mt, st)
-            m = ARENA.get("wino_mw", 4 * pos * 4 * co * c, dev)
-            ws = ARENA.get("ws", _lib.query("mvae_gemm_workspace_bytes", 4 * co, c, t, pos), dev)
-            _lib.call("mvae_winograd_wgrad_gemm", dt.data_ptr(), v.data_ptr(), m.data_ptr(), t, 4 * co, c, mt,
-                      ws.data_ptr(), ws.numel(), st)
-            _lib.call("mvae_winograd_wgrad_output", m.data_ptr(), dkc.data_ptr(), 0.0 if i == 0 else 1.0, 4 * co, c, mt,
-                      st)
-        _lib.call("mvae_winograd_upsample_fold", dkc.data_ptr(), dw.data_ptr(), float(beta), c, co, st)
-        return False
-    if not deferred and _subpixel_upsample(g):
-        nbytes = _lib.query("mvae_conv2d_wgrad_upsample_workspace_bytes", n, h, wd, c, co)
-        ws = ARENA.get("ws", nbytes, dy.device)
-        _lib.call("mvae_conv2d_wgrad_upsample_nhwc", dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db),
-                  float(beta), n, h, wd, c, co, ws.data_ptr(), ws.numel(), st)
-        return db is not None
-    if _wino_wgrad_ok(g, x if lazy is None else lazy.x, dy, dw, dys):
-        # Winograd F(3x3, 2x2): dW = G^T [sum_tiles (A D A^T) (.) (B^T X B)] G (csrc/winograd.hip); the bias gradient is
-        # left to the caller
-        mt = _wtile()
-        pos = (mt + 2) ** 2
-        dev = dy.device
-        dya = dys if dys is not None else dy
-        # the forward's V of this x, per image chunk, when it was kept (same tile size, x unchanged since)
-        kept = {}
-        for e in wino_v or ():
-            if e[1] == mt and e[2] == x.data_ptr() and e[3] == x._version:
-                kept[e[4]] = e[0]
-        kept_d = {}  # the input gradient's pass over dy kept D' too (mvae_winograd_dy_transforms)
-        for e in wino_d or ():
-            if e[1] == mt and e[2] == dya.data_ptr() and e[3] == dya._version:
-                kept_d[e[4]] = e[0]
-        for i, (b0, b1) in enumerate(_wino_chunks(n, h, wd, max(c, co))):
-            nb, t = b1 - b0, _wino_tiles(b1 - b0, h, wd)
-            v = kept.get((b0, b1))
-            dt = kept_d.get((b0, b1))
-            m = ARENA.get("wino_mw", 4 * pos * co * c, dev)
-            ws = ARENA.get("ws", _lib.query("mvae_gemm_workspace_bytes", co, c, t, pos), dev)
-            if dt is None:
-                dt = ARENA.get("wino_d", _wel() * pos * t * co, dev)
-                _lib.call("mvae_winograd_dy_transform", dya[b0:b1].data_ptr(), dt.data_ptr(), nb, h, wd, co,
-                          int(dys is not None), mt, st)
-            if v is None and lazy is not None:  # (the kept V is gone -- a second backward: re-derived, normalized on load)
-                v = ARENA.get("wino_v", _wel() * pos * t * c, dev)
-                _lib.call("mvae_winograd_input_transform_gn", lazy.x[b0:b1].data_ptr(), lazy.scale[b0 * c:].data_ptr(),
-                          lazy.shift[b0 * c:].data_ptr(), lazy.silu, v.data_ptr(), nb, h, wd, c, mt, st)
-            elif v is None:
-                v = ARENA.get("wino_v", _wel() * pos * t * c, dev)
-                _lib.call("mvae_winograd_input_transform", x[b0:b1].data_ptr(), v.data_ptr(), nb, h, wd, c,
-                          int(x_split), mt, st)
-            _lib.call("mvae_winograd_wgrad_gemm", dt.data_ptr(), v.data_ptr(), m.data_ptr(), t, co, c, mt,
-                      ws.data_ptr(), ws.numel(), st)
-            # (image chunks accumulate: the first with the caller's beta, the rest onto it)
-            _lib.call("mvae_winograd_wgrad_output", m.data_ptr(), dw.data_ptr(), float(beta) if i == 0 else 1.0, co, c,
-                      mt, st)
-        return False
-    nbytes = _lib.query("mvae_conv2d_wgrad_workspace_bytes", n, c, co, g.kh, g.kw, ho, wo)
-    ws = ARENA.get("ws", nbytes, dy.device)
-    mode = (1 if g.upsample else 0) | (MVAE_CONV_XSPLIT if x_split else 0)
-    dya = dy
-    if dys is not None and co % 4 == 0:  # (a pre-split dy carries no in-kernel bias sum: the caller sums it)
-        mode |= MVAE_CONV_DYSPLIT
-        dya = dys
-        db = None
-    _lib.call("mvae_conv2d_wgrad_nhwc", dya.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db), float(beta), n, h, wd,
-              c, co, g.kh, g.kw, g.stride, g.pad_t, g.pad_l, ho, wo, mode, ws.data_ptr(), ws.numel(), st)
-    return db is not None
 
 
 def bias_grad_raw(dy2d_ptr, rows, n, out, beta, device, stream):
@@ -1321,18 +1359,18 @@ DYSPLIT_MIN_MACS = 1e11
 
 
 class DyPack:
-    __slots__ = ("bias_ref", "packed", "dx_ref", "dx_version", "dx_shape", "bias_done", "db", "split", "nodx",
+    __slots__ = ("bias_ref", "packed", "dx_ref", "dx_version", "dx_shape", "bias_done", "db", "fmt", "nodx",
                  "copy_ok")
 
-    def __init__(self, bias_ref, split: bool = False):
+    def __init__(self, bias_ref, fmt: str = "packed", copy_ok: bool = False):
         self.bias_ref = bias_ref
-        # False: packed bf16 (bf16-mixed); True: split4_bf16 (3xBF16); "bias": the bias gradient only (a conv that reads
-        # dy in fp32 -- the exact-fp32 Winograd convs, the Upsample conv's Winograd form)
-        self.split = split
+        # ConvPlan.dy_format: "packed" bf16 (bf16-mixed); "split" split4_bf16 (3xBF16); "bias": the bias gradient only
+        # (a conv that reads dy in fp32 -- the Winograd convs)
+        self.fmt = fmt
         self.packed = self.dx_ref = self.dx_version = self.dx_shape = self.db = None
         self.bias_done = False
         self.nodx = False  # the GroupNorm wrote only the copy (its dx has this conv as its only consumer)
-        self.copy_ok = False  # (set by conv2d: every backward path of this conv reads the copy, never the fp32 dy)
+        self.copy_ok = copy_ok  # (ConvPlan.dy_copy_ok: every backward family of the conv reads the copy)
 
     def take(self, dy):
         """(packed dy, bias gradient done, returned bias gradient) when the GroupNorm backward produced them from
@@ -1378,17 +1416,10 @@ def _bwd_side(t: torch.Tensor):
     return side
 
 
-def _overlap_ok(x, dy, g) -> bool:
-    n, c, h, w = x.shape
-    _, co, ho, wo = dy.shape
-    # (image-side convs -- cout 3 / latent channels -- run memory-bound special kernels: c4 lost 0.35 % overlapping them)
-    return not g.pointwise and min(c, co) >= 32 and 2.0 * n * ho * wo * co * c * g.kh * g.kw <= BWD_OVERLAP_MAX_FLOPS
-
-
 class Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, geom: ConvGeom, res_sink=None, x_sink=None, gn_part=None,
-                gn_link=None, dypack=None, grad_on: bool = True, dx_sum=None):
+                gn_link=None, dypack=None, grad_on: bool = True, dx_sum=None, plan: Optional[ConvPlan] = None):
         """grad_on: grad mode at the call (inside forward it is always off): no kept Winograd transform for a conv
         that will have no backward (eval / validation under torch.no_grad)."""
         _check(x, "conv input")
@@ -1400,16 +1431,20 @@ class Conv2dFn(torch.autograd.Function):
         w = _krsc(weight)
         res = nhwc(residual) if residual is not None else None
         want_w = bool(weight.requires_grad and grad_on)
-        if lazy is not None and not _lazy_wino(lazy, x, w, bias, res, geom, gn_part, want_w):
-            x, lazy = lazy.materialize(), None  # (the conv cannot normalize on load: the GroupNorm output is written)
+        if plan is None:
+            plan = plan_conv(geom, *x.shape, w.shape[0], _MATH[0])
+        # (deferred only while the forward normalizes on load and a wanted weight gradient is the Winograd one)
+        if lazy is not None and not (_fwd_family(plan, x, w, bias, res, xs, xb16, gn_part, lazy) == "wino" and
+                                     (not want_w or "wino" in plan.wgrad)):
+            x, lazy = lazy.materialize(), None
         if lazy is None:
             x = nhwc(x)
         keep = [] if (WINOGRAD_KEEP_V or lazy is not None) and want_w else None
-        y = conv2d_forward_raw(x, w, bias, res, geom, xs, gn_part, x_bf16=xb16, keep_v=keep, lazy=lazy)
+        y = conv2d_forward_raw(x, w, bias, res, geom, xs, gn_part, x_bf16=xb16, keep_v=keep, lazy=lazy, plan=plan)
         ctx.wino_v = keep if keep else None
         ctx.lazy = lazy  # (the weight gradient re-derives V from it if the kept one is gone: a second backward)
-        ctx.math = _MATH[0]  # the backward GEMMs run in the forward's arithmetic
-        ctx.geom = geom
+        ctx.math = plan.math  # the backward GEMMs run in the forward's arithmetic, on the forward's plan
+        ctx.geom, ctx.plan = geom, plan
         ctx.x_split = xs
         ctx.x_bf16 = xb16
         ctx.has_bias = bias is not None
@@ -1431,7 +1466,7 @@ class Conv2dFn(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, dy):
         x, w = ctx.saved_tensors
-        g = ctx.geom
+        g, plan = ctx.geom, ctx.plan
         dy = nhwc(dy)
         dx = dw_ret = db_ret = dres = None
         link = ctx.gn_link
@@ -1444,9 +1479,9 @@ class Conv2dFn(torch.autograd.Function):
         dys = None
         if got is not None:  # from the GroupNorm backward that produced dy: the bias gradient (column sums of its dx)
             taken, bias_done, db_ret = got
-            if not ctx.dypack.split:  # ... with dy packed to bf16
+            if ctx.dypack.fmt == "packed":  # ... with dy packed to bf16
                 dyb = taken
-            elif ctx.dypack.split != "bias":  # ... with dy pre-split ("bias": the bias gradient alone)
+            elif ctx.dypack.fmt == "split":  # ... with dy pre-split ("bias": the bias gradient alone)
                 dys = taken
             if not want_b:
                 db_ret = None
@@ -1460,7 +1495,8 @@ class Conv2dFn(torch.autograd.Function):
             bt = _main_grad(ctx.bias_ref) if want_b else None
             if want_b and bt is None:
                 db_ret = torch.empty(dy.shape[1], device=dy.device, dtype=torch.float32)
-            dyb, bias_done = pack_dy(dy, g, w.shape[1], bt if bt is not None else db_ret, 1.0 if bt is not None else 0.0)
+            dyb, bias_done = pack_dy(dy, g, w.shape[1], bt if bt is not None else db_ret, 1.0 if bt is not None else 0.0,
+                                     plan)
             if not bias_done:
                 db_ret = None
         if dys is None and not g.pointwise and not _subpixel_upsample(g) and dyb is None:
@@ -1470,24 +1506,19 @@ class Conv2dFn(torch.autograd.Function):
         def wgrad():
             nonlocal dw_ret, bias_done
             tgt = _main_grad(ctx.weight_ref)
-            btgt = _main_grad(ctx.bias_ref) if want_b and not bias_done else None
-            want_b_w = want_b and not bias_done
-            xs, xb16 = ctx.x_split, ctx.x_bf16
-            lz = ctx.lazy
-            if tgt is not None and (not want_b_w or btgt is not None):
-                fused = conv2d_wgrad_raw(dy, x, tgt, 1.0, g, btgt, x_split=xs, dys=dys, dyb=dyb, x_bf16=xb16,
-                                         wino_v=ctx.wino_v, wino_d=dkeep, lazy=lz)
-                bias_done = bias_done or fused
-            elif tgt is not None:
-                conv2d_wgrad_raw(dy, x, tgt, 1.0, g, x_split=xs, dys=dys, dyb=dyb, x_bf16=xb16, wino_v=ctx.wino_v,
-                                 wino_d=dkeep, lazy=lz)
-            else:
+            if tgt is None:
                 dw_ret = torch.empty_like(w, memory_format=CL)
-                conv2d_wgrad_raw(dy, x, dw_ret, 0.0, g, x_split=xs, dys=dys, dyb=dyb, x_bf16=xb16,
-                                 wino_v=ctx.wino_v, wino_d=dkeep, lazy=lz)
+            # (the fused kernels' bias gradient goes with a weight gradient into the flat slots only)
+            btgt = _main_grad(ctx.bias_ref) if tgt is not None and want_b and not bias_done else None
+            fused = conv2d_wgrad_raw(dy, x, dw_ret if tgt is None else tgt, 0.0 if tgt is None else 1.0, g, btgt,
+                                     x_split=ctx.x_split, dys=dys, dyb=dyb, x_bf16=ctx.x_bf16, wino_v=ctx.wino_v,
+                                     wino_d=dkeep, lazy=ctx.lazy, plan=plan)
+            bias_done = bias_done or fused
 
+        # (image-side convs -- cout 3 / latent channels -- run memory-bound special kernels: c4 lost 0.35 % overlapping them)
         side = _bwd_side(dy) if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and \
-            _main_grad(ctx.weight_ref) is not None and _overlap_ok(x, dy, g) else None
+            _main_grad(ctx.weight_ref) is not None and not g.pointwise and min(plan.c, plan.co) >= 32 and \
+            plan.ref <= BWD_OVERLAP_MAX_FLOPS else None
         if side is not None:
             # the weight gradient on the side stream, concurrent with the input gradient (the arena keys its scratch
             # buffers by stream, so the two never share one); joined before returning
@@ -1500,10 +1531,8 @@ class Conv2dFn(torch.autograd.Function):
             ev_join.record(stream)
         # both gradients on the Winograd form, one after the other: the input gradient's pass over dy also writes the
         # weight gradient's transformed dy (mvae_winograd_dy_transforms), instead of a second pass
-        n_, c_, h_, w_ = x.shape
         dkeep = [] if (WINOGRAD_DY2 and side is None and dyb is None and ctx.needs_input_grad[0] and
-                       ctx.needs_input_grad[1] and WINOGRAD_WGRAD and not g.pointwise and
-                       (_wino_ok(g, n_, h_, w_, c_, w.shape[0]) or _wino_ups_ok(g, n_, h_, w_, c_, w.shape[0]))) else None
+                       ctx.needs_input_grad[1] and _wgrad_wino_on(plan)) else None
         acc = ctx.dx_sum
         if ctx.needs_input_grad[0] and acc is not None:
             # one of several 1x1 convs reading the same input: accumulate into the shared input gradient (every one of
@@ -1513,14 +1542,14 @@ class Conv2dFn(torch.autograd.Function):
             first = acc.buf is None
             if first:
                 acc.buf = torch.empty(tuple(x.shape), device=dy.device, dtype=torch.float32, memory_format=CL)
-            conv2d_dgrad_raw(dy, w, x.shape, g, out=acc.buf, beta=0.0 if first else 1.0)
+            conv2d_dgrad_raw(dy, w, x.shape, g, out=acc.buf, beta=0.0 if first else 1.0, plan=plan)
             acc.left -= 1
             dx = None
             if acc.left == 0:  # (the last of them returns the sum; re-armed for a retained graph's next backward)
                 dx, acc.buf, acc.left = acc.buf, None, acc.n
         elif ctx.needs_input_grad[0]:
             dx = conv2d_dgrad_raw(dy, w, x.shape, g, link if ctx.x_sink is None else None, dys=dys, dyb=dyb,
-                                  dkeep=dkeep)
+                                  dkeep=dkeep, plan=plan)
             if ctx.x_sink is not None and ctx.x_sink.park(dx):
                 dx = None
         if side is not None:
@@ -1544,7 +1573,7 @@ class Conv2dFn(torch.autograd.Function):
             _grad_done(ctx.weight_ref)
         if want_b and db_ret is None:
             _grad_done(ctx.bias_ref)
-        return dx, dw_ret, db_ret, dres, None, None, None, None, None, None, None, None
+        return dx, dw_ret, db_ret, dres, None, None, None, None, None, None, None, None, None
 
 
 # The GroupNorm statistics of a conv output emitted by its GEMM epilogue travel with the output tensor
@@ -1553,58 +1582,30 @@ GN_PART_ATTR = "_mvae_gn_part"
 GN_FUSED_STATS = os.environ.get("MVAE_NO_GN_FUSED") is None and os.environ.get("MVAE_NO_VEC_EPI") is None
 
 
-def _conv_macs(x, weight, geom: ConvGeom) -> float:
-    n, c, h, w = x.shape
-    ho, wo = geom.out_hw(h, w)
-    return float(n) * ho * wo * weight.shape[0] * c * geom.kh * geom.kw
-
-
 def conv2d(x, weight, bias, geom: ConvGeom, residual=None, res_sink=None, x_sink=None, gn_stats: bool = False,
            gn_bias: bool = False, dx_sum=None):
     """gn_stats=True: the output feeds a Normalize (encoder_decoder.py:28-33) -- emit its statistics from the
     conv's epilogue so the GroupNorm skips its statistics pass (plain implicit-GEMM convs only)."""
+    n, c, h, w = x.shape
+    co = weight.shape[0]
+    plan = plan_conv(geom, n, c, h, w, co, _MATH[0])
     part = None
-    if gn_stats and GN_FUSED_STATS and not geom.pointwise and not _subpixel_upsample(geom) and x.shape[1] % 4 == 0:
-        n, _, h, w = x.shape
+    if gn_stats and GN_FUSED_STATS and not geom.pointwise and not _subpixel_upsample(geom) and c % 4 == 0:
         ho, wo = geom.out_hw(h, w)
-        co = weight.shape[0]
-        if (ho * wo) % 32 == 0 and co % 4 == 0 and _al16(x, weight) and (bias is None or _al16(bias)) and (
-                residual is None or _al16(residual)):
+        if (ho * wo) % 32 == 0 and co % 4 == 0 and _al16(x, weight, bias, residual):
             part = torch.empty(n * ho * wo // 32 * (co // 4) * 2, device=x.device, dtype=torch.float64)
     link = getattr(x, GN_BWD_ATTR, None)
     if link is not None and not link.matches(x):
         link = None
-    dyp = None
-    # (a Winograd conv of the bf16-mixed mode reads dy in fp32 or 3xBF16-split form, not packed: the GroupNorm backward
-    # writes it split, as in the 3xBF16 mode)
-    wino_any = x.dim() == 4 and _wino_ok(geom, x.shape[0], x.shape[2], x.shape[3], x.shape[1], weight.shape[0])
-    wino_bf16 = _MATH[0] == 1 and wino_any
-    # (a Winograd conv splits / rounds dy in its own memory-bound transform: the GroupNorm backward then writes no
-    # second copy of dx, only the bias gradient)
-    wino_fp32_dy = WINOGRAD_DY_FP32 and wino_any and not _subpixel_upsample(geom)
-    if gn_stats and DYPACK and _dma_fmt() == 2 and not wino_bf16 and not geom.pointwise and weight.shape[0] % 8 == 0 and \
-            geom.kh * geom.kw <= 32 and torch.is_grad_enabled():
-        dyp = DyPack(bias)
-        # (the LDS-DMA input / weight gradients read the packed copy; GroupNorm-partials epilogues and odd channel
-        # counts fall back to kernels that read the fp32 dy)
-        dyp.copy_ok = not GN_BWD_FUSED and x.shape[1] % 8 == 0 and not geom.upsample
-    elif gn_stats and DYSPLIT and ((_dma_fmt() == 0 and _MATH[0] == 0) or wino_bf16) and not wino_fp32_dy and \
-            not geom.pointwise and \
-            not _subpixel_upsample(geom) and weight.shape[0] % 4 == 0 and geom.kh * geom.kw <= 32 and \
-            torch.is_grad_enabled() and _conv_macs(x, weight, geom) >= DYSPLIT_MIN_MACS:
-        dyp = DyPack(bias, split=True)
-        dyp.copy_ok = not GN_BWD_FUSED  # (the 3xBF16 GEMMs and Winograd transforms read the split copy)
-    elif (gn_stats or gn_bias) and DYBIAS and bias is not None and bias.requires_grad and torch.is_grad_enabled() and \
-            x.dim() == 4 and weight.shape[0] % 4 == 0 and (
-                (_MATH[0] == 2 and not _subpixel_upsample(geom) and wino_any) or wino_fp32_dy or
-                _wino_ups_ok(geom, x.shape[0], x.shape[2], x.shape[3], x.shape[1], weight.shape[0])):
-        # a Winograd conv reading dy in fp32 whose output feeds a GroupNorm: the bias gradient comes out of that
-        # GroupNorm's backward (column sums of its dx) instead of a separate pass over dy
-        dyp = DyPack(bias, split="bias")
+    # the GroupNorm on the output writes its dx -- this conv's dy -- as the planned backward reads it (gn_bias: bias only)
+    fmt = plan.dy_format if gn_stats else "bias" if gn_bias and plan.dy_bias else None
+    if fmt == "bias" and not (bias is not None and bias.requires_grad):
+        fmt = None
+    dyp = DyPack(bias, fmt, plan.dy_copy_ok and fmt == plan.dy_format) if fmt and torch.is_grad_enabled() else None
     if dx_sum is not None and not (DX_SUM and geom.pointwise and torch.is_grad_enabled() and x_sink is None):
         dx_sum = None
     y = Conv2dFn.apply(x, weight, bias, residual, geom, res_sink, x_sink, part, link, dyp, torch.is_grad_enabled(),
-                       dx_sum)
+                       dx_sum, plan)
     if part is not None:
         setattr(y, GN_PART_ATTR, (part, y._version))
     if dyp is not None:
@@ -1723,9 +1724,9 @@ class GroupNormFn(torch.autograd.Function):
         gpart = ctx.link.take(dy) if ctx.link is not None and drop_p == 0.0 else None
         # algorithmic HBM bytes: read x, dy (and the residual branch's gradient when it is summed here); write dx
         req = ctx.dypack if ctx.dypack is not None and _al16(dy, dx) and (add is None or _al16(add)) else None
-        if req is not None and gpart is not None and req.split is False:
+        if req is not None and gpart is not None and req.fmt == "packed":
             req = None  # (the backward from the conv's partials writes split4 dy or the bias column sums only)
-        bias_only = req is not None and req.split == "bias"
+        bias_only = req is not None and req.fmt == "bias"
         if bias_only and not (req.bias_ref is not None and req.bias_ref.requires_grad):
             req = None
         packed = tgt = cs = None
@@ -1737,7 +1738,7 @@ class GroupNormFn(torch.autograd.Function):
         elif req is not None:
             # also dx as packed bf16 / split4 and the producing conv's bias gradient (DyPack)
             # packed bf16: 2 B per element; split4_bf16: 4 B per element, dx's layout (an fp32-sized buffer)
-            packed = (torch.empty_like(x, memory_format=CL) if req.split else
+            packed = (torch.empty_like(x, memory_format=CL) if req.fmt == "split" else
                       torch.empty(x.numel() * 2, device=x.device, dtype=torch.uint8))
             bref = req.bias_ref
             if bref is not None and bref.requires_grad:
@@ -1771,7 +1772,7 @@ class GroupNormFn(torch.autograd.Function):
                           _ptr(db), n, h * w, c, groups, silu, drop_p, seed, ws.data_ptr(), ws.numel(), tgt.data_ptr(),
                           0.0, cs.data_ptr(), cs.numel(), _stream(x))
             elif req is not None:
-                _lib.call("mvae_group_norm_bwd_split_nhwc" if req.split else "mvae_group_norm_bwd_pack_nhwc",
+                _lib.call("mvae_group_norm_bwd_split_nhwc" if req.fmt == "split" else "mvae_group_norm_bwd_pack_nhwc",
                           x.data_ptr(), dy.data_ptr(), gamma.data_ptr(),
                           beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dxp, _ptr(add), _ptr(dg),
                           _ptr(db), n, h * w, c, groups, silu, drop_p, seed, ws.data_ptr(), ws.numel(),
@@ -1816,10 +1817,10 @@ def group_norm(x, gamma, beta, groups, eps=1e-6, silu=False, drop_p=0.0, seed=0,
     ops.conv2d (3x3/stride-1, C % 4 == 0) -- the output is then written pre-split for the GEMM (GroupNorm -> conv is
     the ResnetBlock / norm_out pattern, encoder_decoder.py:141-163, :318-328); in the bf16-mixed mode, with a known
     output channel count that is a multiple of 8, packed bf16 for the LDS-DMA GEMM."""
-    packed = bool(for_conv and not isinstance(for_conv, bool) and int(for_conv) % 8 == 0 and _bf16_dma() and
-                  x.shape[1] % 8 == 0 and _al16(x) and _dma_ok(9.0 * x.numel() * int(for_conv)) and
-                  not (x.dim() == 4 and _wino_ok(G3, x.shape[0], x.shape[2], x.shape[3], x.shape[1], int(for_conv))))
-    split = _dma_fmt() if packed else int(bool(for_conv and ACT_SPLIT and _splits_ok() and not _bf16_dma() and
+    # (the consuming conv is 3x3 / stride 1 / pad 1: for_conv callers; its plan says how it reads this output)
+    plan = plan_conv(G3, *x.shape, int(for_conv), _MATH[0]) if for_conv and not isinstance(for_conv, bool) else None
+    packed = plan is not None and plan.fwd[0] == "dma" and plan.co % 8 == 0 and _al16(x)
+    split = _dma_fmt() if packed else int(bool(for_conv and ACT_SPLIT and _splits_ok() and _dma_fmt() == 0 and
                                                 x.shape[1] % 4 == 0))
     part = getattr(x, GN_PART_ATTR, None)
     if part is not None:
@@ -1834,18 +1835,16 @@ def group_norm(x, gamma, beta, groups, eps=1e-6, silu=False, drop_p=0.0, seed=0,
         delattr(x, DYPACK_ATTR)  # one GroupNorm per conv output
         dyp = dyp[0] if dyp[1] == x._version and x.is_contiguous(memory_format=CL) and _al16(x) else None
     lazy = None
-    if (WINOGRAD_GN and for_conv and not isinstance(for_conv, bool) and drop_p == 0.0 and not packed and
-            x.dim() == 4 and _al16(x) and WINOGRAD_WGRAD):
+    if plan is not None and plan.gn_on_load and drop_p == 0.0 and _al16(x):
         n, c, h, w = x.shape
-        if _wino_ok(G3, n, h, w, c, int(for_conv)):  # (the consuming conv is 3x3 / stride 1 / pad 1: for_conv callers)
-            lazy, split = LazyGn(x, silu), 0
-            # the conv's Winograd input-gradient output transform also emits this GroupNorm's backward partials
-            # (mvae_winograd_output_gnbwd: one extra read of x there) where the backward would otherwise make a partial
-            # pass over x and dy (its streaming chain: the large levels, whose producing conv takes dy pre-split)
-            if (link is None and WINOGRAD_GN_LINK and x.requires_grad and dyp is not None and dyp.split is not False and
-                    _wino_blocks(h, w) and c % groups == 0 and (c // groups) % 4 == 0 and
-                    _lib.query("mvae_group_norm_bwd_streaming", n, h * w, c, groups, 1)):
-                link = GnBwdLink(groups, silu)
+        lazy, split = LazyGn(x, silu), 0
+        # the conv's Winograd input-gradient output transform also emits this GroupNorm's backward partials
+        # (mvae_winograd_output_gnbwd: one extra read of x there) where the backward would otherwise make a partial
+        # pass over x and dy (its streaming chain: the large levels, whose producing conv takes dy pre-split)
+        if (link is None and WINOGRAD_GN_LINK and x.requires_grad and dyp is not None and dyp.fmt != "packed" and
+                plan.blocks and c % groups == 0 and (c // groups) % 4 == 0 and
+                _lib.query("mvae_group_norm_bwd_streaming", n, h * w, c, groups, 1)):
+            link = GnBwdLink(groups, silu)
     y = GroupNormFn.apply(x, gamma, beta, groups, eps, silu, drop_p, seed, split, grad_sink, part, link, dyp, lazy,
                           conv_dy_only)
     if lazy is not None:
