@@ -449,6 +449,20 @@ int mvae_multi_tensor_adam(float* params, float* grads, float* exp_avg, float* e
                            double beta2, float eps, double weight_decay, int decoupled, void* workspace,
                            size_t workspace_bytes, float* scalars, void* stream);
 size_t mvae_multi_tensor_adam_workspace_bytes(int nchunks, int ntensors);
+/* The same step (same arguments, workspace and three launches) that also keeps an exponential moving average of the
+ * weights, the reference's exponential_moving_average helper (src/utils/training_utils.py:221-227): after params has
+ * its new value, ema = ema * d + omd * params with d = (float)ema_decay, omd = (float)(1.0 - ema_decay), in the same
+ * pass. ema is laid out like params. Every tensor is averaged, also one with used[t] == 0 (which skips Adam, as
+ * above). params, grads, the moments, step and scalars come out as from mvae_multi_tensor_adam. 0 <= ema_decay < 1. */
+int mvae_multi_tensor_adam_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                               const int* chunk_tensor, const long long* chunk_start, const int* chunk_len,
+                               int nchunks, const int* tensor_chunk_begin, int ntensors, const int* used,
+                               int* step, float grad_scale, float max_norm, int do_clip, double lr, double beta1,
+                               double beta2, float eps, double weight_decay, int decoupled, void* workspace,
+                               size_t workspace_bytes, float* scalars, float* ema, double ema_decay, void* stream);
+/* Exchange two device buffers of n floats in place (16-B accesses when both are 16-B aligned): the averaged weights
+ * go under the model, and back, without a temporary. MVAE_EINVAL for a null pointer or n == 0 (nothing is launched). */
+int mvae_swap_buffers(float* a, float* b, size_t n, void* stream);
 
 /* ---- perceptual loss (LPIPSLoss, src/losses/vae_losses.py:67-94; lpips 0.1.4 net="alex"/"vgg") ----
  * y = (a*x + b - shift[c]) * inv_scale[c]: `inputs*2-1` (a=2, b=-1) then lpips' ScalingLayer. */

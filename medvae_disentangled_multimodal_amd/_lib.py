@@ -107,6 +107,9 @@ SIGNATURES = {
     "mvae_recon_bwd": (I, [I, P, P, P, D, P, L, P]),
     "mvae_multi_tensor_adam": (I, [P, P, P, P, P, P, P, I, P, I, P, P, F, F, I, D, D, D, F, D, I, P, Z, P, P]),
     "mvae_multi_tensor_adam_workspace_bytes": (Z, [I, I]),
+    "mvae_multi_tensor_adam_ema": (I, [P, P, P, P, P, P, P, I, P, I, P, P, F, F, I, D, D, D, F, D, I, P, Z, P, P, D,
+                                       P]),
+    "mvae_swap_buffers": (I, [P, P, Z, P]),
     "mvae_lpips_scale": (I, [P, P, L, I, F, F, P, P, P]),
     "mvae_lpips_scale_bwd": (I, [P, P, L, I, F, P, P]),
     "mvae_relu_fwd": (I, [P, P, L, P]),

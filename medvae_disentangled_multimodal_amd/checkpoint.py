@@ -8,6 +8,12 @@ order, `epoch`, `global_step`, `lr_schedulers` -- so the reference can resume fr
 reference checkpoint loads here (weights and Adam moments land in the flat buffers).
 Loading uses `torch.load(weights_only=True)`: nothing in the file is executed; a checkpoint that
 needs arbitrary unpickling is refused.
+
+A module that keeps an exponential moving average of its weights (optimizer_config["ema_decay"]) adds ONE top-level
+key, `ema_state = {"decay": float, "weights": {name: logical-OIHW cpu tensor}}` (parameter names as in
+`model.named_parameters()`); every other key is what it is without the average, so the reference still loads the file
+strictly. `weights="ema"` writes the averaged weights as `state_dict["model.*"]` instead, without optimizer states: a
+file the reference's generate.py / quick_generate.py load as the model to sample from.
 """
 from __future__ import annotations
 
@@ -39,12 +45,28 @@ def _torch_optimizer_state(opt, flat) -> Dict[str, Any]:
     return {"state": state, "param_groups": [group]}
 
 
-def lightning_checkpoint(module, epoch: int = 0) -> Dict[str, Any]:
+def _ema_weights(module) -> "OrderedDict[str, torch.Tensor]":
+    """{parameter name: averaged weight}, logical shapes (conv weights OIHW, contiguous), on the CPU."""
+    opt, flat = module.optimizer, module.flat
+    if opt is None or getattr(opt, "ema", None) is None:
+        raise RuntimeError('checkpoint: the module keeps no EMA (optimizer_config["ema_decay"] is not set, or no '
+                           "optimizer is configured yet)")
+    if getattr(module, "_in_ema_scope", False):
+        raise RuntimeError("checkpoint: called inside ema_scope() (the weights and their average are exchanged)")
+    return OrderedDict((n, FlatParameters._view(opt.ema, off, p).detach().contiguous().cpu())
+                       for n, p, off in zip(flat.names, flat.params, flat.offsets))
+
+
+def lightning_checkpoint(module, epoch: int = 0, weights: str = "live") -> Dict[str, Any]:
     """The dict `trainer.save_checkpoint` would write for this module: the LightningModule's own state dict
     (`model.*` and the criterion's `criterion.*` -- LPIPS network, discriminator weights and BatchNorm
     buffers), one optimizer state per optimizer (the discriminator's Adam second, lightning_module.py:
     427-433). Lightning checkpoints at optimisation-step boundaries only: a module inside a gradient-accumulation
-    window (micro-batches in the flat gradient, no step yet) is refused, since the file could not hold that state."""
+    window (micro-batches in the flat gradient, no step yet) is refused, since the file could not hold that state.
+    weights="ema": the averaged weights in place of the live ones in `state_dict`, and no optimizer states (a model to
+    evaluate or sample from, not to resume)."""
+    if weights not in ("live", "ema"):
+        raise ValueError(f'checkpoint: weights must be "live" or "ema", got {weights!r}')
     if getattr(module, "accumulating", False):
         raise RuntimeError("checkpoint: a gradient-accumulation window is open (accumulate_grad_batches = "
                            f"{module.accumulate_grad_batches}); save at a step boundary, after the window's last "
@@ -56,6 +78,14 @@ def lightning_checkpoint(module, epoch: int = 0) -> Dict[str, Any]:
     ck = {"epoch": int(epoch), "global_step": int(getattr(module, "global_step_count", 0)),
           "pytorch-lightning_version": LIGHTNING_VERSION, "state_dict": sd, "loops": {}, "callbacks": {},
           "lr_schedulers": [], "optimizer_states": []}
+    if weights == "ema":
+        for n, v in _ema_weights(module).items():
+            sd[f"model.{n}"] = v
+        return ck
+    if getattr(module, "_in_ema_scope", False):
+        raise RuntimeError("checkpoint: called inside ema_scope() (the weights and their average are exchanged)")
+    if module.optimizer is not None and getattr(module.optimizer, "ema", None) is not None:
+        ck["ema_state"] = {"decay": float(module.optimizer.ema_decay), "weights": dict(_ema_weights(module))}
     if module.optimizer is not None:
         ck["optimizer_states"] = [_torch_optimizer_state(module.optimizer, module.flat)]
         if getattr(module, "optimizer_d", None) is not None:
@@ -65,14 +95,18 @@ def lightning_checkpoint(module, epoch: int = 0) -> Dict[str, Any]:
     return ck
 
 
-def save_checkpoint(module, path: str, epoch: int = 0):
-    torch.save(lightning_checkpoint(module, epoch), path)
+def save_checkpoint(module, path: str, epoch: int = 0, weights: str = "live"):
+    torch.save(lightning_checkpoint(module, epoch, weights), path)
 
 
 def load_checkpoint(module, ckpt, strict: bool = True, load_optimizer: bool = True):
     """Load a Lightning checkpoint (path or dict) of the reference's VAELightningModule (or of this
     one) into `module`: model weights (into the flat parameter buffer) and, when present and an
-    optimizer is configured, the Adam/AdamW moments and step counts."""
+    optimizer is configured, the Adam/AdamW moments and step counts. A module that keeps an EMA of its weights takes
+    the checkpoint's `ema_state` weights into its flat EMA buffer, or, from a checkpoint without one, restarts the
+    average from the loaded weights; a module without EMA ignores the key."""
+    if getattr(module, "_in_ema_scope", False):
+        raise RuntimeError("load_checkpoint: called inside ema_scope()")
     if isinstance(ckpt, str):
         ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
     module._graph = None  # a captured step froze the old hyper-parameters (betas / eps / lr) as launch values
@@ -91,8 +125,28 @@ def load_checkpoint(module, ckpt, strict: bool = True, load_optimizer: bool = Tr
         _load_optimizer_state(module.optimizer, module.flat, states[0])
         if len(states) > 1 and getattr(module, "optimizer_d", None) is not None:
             _load_optimizer_state(module.optimizer_d, module.flat_d, states[1])
+    if module.optimizer is None and ckpt.get("ema_state") and \
+            getattr(module, "optimizer_config", {}).get("ema_decay") is not None:
+        module.configure_optimizers()  # (the average lives in the optimizer's flat EMA buffer)
+    opt = module.optimizer
+    if opt is not None and getattr(opt, "ema", None) is not None:
+        _load_ema(opt, module.flat, (ckpt.get("ema_state") or {}).get("weights"), strict)
     module.global_step_count = int(ckpt.get("global_step", 0))
     return ckpt
+
+
+def _load_ema(opt, flat, weights, strict: bool):
+    with torch.no_grad():
+        if weights is None:
+            opt.ema.copy_(flat.data)
+            return
+        missing = [n for n in flat.names if n not in weights]
+        if strict and (missing or len(weights) != len(flat.names)):
+            raise RuntimeError(f"checkpoint: ema_state does not match the model's parameters (missing {missing[:4]}, "
+                               f"unexpected {[n for n in weights if n not in flat.names][:4]})")
+        for n, p, off in zip(flat.names, flat.params, flat.offsets):
+            # (a parameter the file has no average for starts from its loaded weight)
+            FlatParameters._view(opt.ema, off, p).copy_(weights[n] if n in weights else p.detach())
 
 
 def _load_optimizer_state(opt, flat, st):

@@ -7,6 +7,13 @@
 //       (lightning_module.py:390-408 -> torch.optim single-tensor arithmetic)
 // Tensors whose gradient is absent this step (`used[t] == 0`, e.g. heads of modalities that are
 // not in the batch) are skipped exactly like torch skips params with grad None.
+//
+// mvae_multi_tensor_adam_ema: the same three launches, the third also keeping an exponential moving average of the
+// weights (the reference's exponential_moving_average helper, src/utils/training_utils.py:221-227:
+// ema.mul_(decay).add_(param, alpha=1 - decay) over ALL parameters) in a flat buffer laid out like the parameters:
+// after p has its new value, ema = ema * d + omd * p -- one more read and one more write per element (36 instead of
+// 28 B/param) in the pass that already holds p in registers. A tensor without a gradient this step skips Adam and
+// still averages. mvae_swap_buffers exchanges two flat buffers in place (the averaged weights under the model).
 #include "common.h"
 
 namespace mvae {
@@ -95,14 +102,37 @@ __global__ void __launch_bounds__(256) mt_finalize_kernel(MtArgs a, float max_no
 // 1.f - 0.999f is 0.00099998713, 1.3e-5 off, and exp_avg_sq carried that error in every element
 // ... and the bias corrections 1 - beta^step from the double betas (torch: Python floats), consistent with them; the
 // step size lr / bias_correction1 and the decoupled decay 1 - lr * wd likewise from the double lr and weight decay
+// EMA: after p has its new value, ema = ema * d + omd * p with d and omd = 1 - d rounded from the double decay (as w and
+// omb2 are); a tensor that is not `used` this step takes that update alone.
+template <bool EMA>
 __global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, double lr, double b1d, double b2d, float eps, double wdd,
-                                                      int decoupled) {
+                                                      int decoupled, float* ema, double emad) {
   const float b2 = (float)b2d, w = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d), wd = (float)wdd;
+  const float d = (float)emad, omd = (float)(1.0 - emad);
   const int ch = blockIdx.x;
   const int t = a.chunk_tensor[ch];
-  if (!a.used[t]) return;
   const long long s = a.chunk_start[ch];
   const int len = a.chunk_len[ch];
+  if (!a.used[t]) {
+    if constexpr (EMA) {
+      const int body = (s & 3) == 0 ? (len & ~3) : 0;
+      for (int i = threadIdx.x * 4; i < body; i += blockDim.x * 4) {
+        const long long e = s + i;
+        const float4 p4 = *(const float4*)(a.p + e);
+        float4 e4 = *(const float4*)(ema + e);
+        e4.x = e4.x * d + omd * p4.x;
+        e4.y = e4.y * d + omd * p4.y;
+        e4.z = e4.z * d + omd * p4.z;
+        e4.w = e4.w * d + omd * p4.w;
+        *(float4*)(ema + e) = e4;
+      }
+      for (int i = body + threadIdx.x; i < len; i += blockDim.x) {
+        const long long e = s + i;
+        ema[e] = ema[e] * d + omd * a.p[e];
+      }
+    }
+    return;
+  }
   const bool zero = a.bad[t] != 0;
   const float coef = a.scalars[1];
   const int step = a.step[t];
@@ -138,6 +168,14 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, double lr, doubl
     *(float4*)(a.p + e) = p4;
     *(float4*)(a.m + e) = m4;
     *(float4*)(a.v + e) = v4;
+    if constexpr (EMA) {
+      float4 e4 = *(const float4*)(ema + e);
+      e4.x = e4.x * d + omd * p4.x;
+      e4.y = e4.y * d + omd * p4.y;
+      e4.z = e4.z * d + omd * p4.z;
+      e4.w = e4.w * d + omd * p4.w;
+      *(float4*)(ema + e) = e4;
+    }
   }
   for (int i = body + threadIdx.x; i < len; i += blockDim.x) {
     const long long e = s + i;
@@ -155,6 +193,25 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, double lr, doubl
     a.m[e] = m;
     a.v[e] = v;
     a.p[e] = p;
+    if constexpr (EMA) ema[e] = ema[e] * d + omd * p;
+  }
+}
+
+// a <-> b in place: 16-B loads and stores over a grid-stride loop (both buffers 16-B aligned), scalar tail
+__global__ void __launch_bounds__(256) swap_buffers_kernel(float* a, float* b, size_t n, int vec) {
+  const size_t body = vec ? (n & ~(size_t)3) : 0;
+  const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
+  for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < body; i += stride) {
+    const float4 x = *(const float4*)(a + i), y = *(const float4*)(b + i);
+    *(float4*)(a + i) = y;
+    *(float4*)(b + i) = x;
+  }
+  if (blockIdx.x == 0) {
+    for (size_t i = body + threadIdx.x; i < n; i += blockDim.x) {
+      const float x = a[i];
+      a[i] = b[i];
+      b[i] = x;
+    }
   }
 }
 
@@ -162,17 +219,13 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(MtArgs a, double lr, doubl
 
 using namespace mvae;
 
-extern "C" {
-
-// One optimizer step over flat buffers. chunk tables / tensor_chunk_begin describe how the flat
-// buffer splits into tensors (host-built once). Workspace: chunk_sumsq (double[nchunks]),
-// chunk_bad (int[nchunks]), bad (int[T]); scalars: float[2] out (total norm, clip coef).
-int mvae_multi_tensor_adam(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int* chunk_tensor,
-                           const long long* chunk_start, const int* chunk_len, int nchunks,
-                           const int* tensor_chunk_begin, int ntensors, const int* used, int* step, float grad_scale,
-                           float max_norm, int do_clip, double lr, double beta1, double beta2, float eps,
-                           double weight_decay, int decoupled, void* workspace, size_t workspace_bytes, float* scalars,
-                           void* stream) {
+// the three launches of one step (ema == nullptr: no averaged copy)
+static int mt_adam_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int* chunk_tensor,
+                          const long long* chunk_start, const int* chunk_len, int nchunks,
+                          const int* tensor_chunk_begin, int ntensors, const int* used, int* step, float grad_scale,
+                          float max_norm, int do_clip, double lr, double beta1, double beta2, float eps,
+                          double weight_decay, int decoupled, void* workspace, size_t workspace_bytes, float* scalars,
+                          float* ema, double ema_decay, void* stream) {
   const size_t need = (size_t)nchunks * (sizeof(double) + sizeof(int)) + (size_t)ntensors * sizeof(int) + 64;
   if (nchunks <= 0 || ntensors <= 0) { set_error("adam: empty"); return MVAE_EINVAL; }
   if (workspace_bytes < need) { set_error("adam: workspace too small"); return MVAE_EWORKSPACE; }
@@ -187,8 +240,54 @@ int mvae_multi_tensor_adam(float* params, float* grads, float* exp_avg, float* e
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mt_chunk_stats_kernel, dim3(nchunks), dim3(256), 0, st, a);
   hipLaunchKernelGGL(mt_finalize_kernel, dim3(1), dim3(256), 0, st, a, max_norm, do_clip);
-  hipLaunchKernelGGL(mt_adam_kernel, dim3(nchunks), dim3(256), 0, st, a, lr, beta1, beta2, eps, weight_decay,
-                     decoupled);
+  if (ema)
+    hipLaunchKernelGGL(mt_adam_kernel<true>, dim3(nchunks), dim3(256), 0, st, a, lr, beta1, beta2, eps, weight_decay,
+                       decoupled, ema, ema_decay);
+  else
+    hipLaunchKernelGGL(mt_adam_kernel<false>, dim3(nchunks), dim3(256), 0, st, a, lr, beta1, beta2, eps, weight_decay,
+                       decoupled, (float*)nullptr, 0.0);
+  return launch_status();
+}
+
+extern "C" {
+
+// One optimizer step over flat buffers. chunk tables / tensor_chunk_begin describe how the flat
+// buffer splits into tensors (host-built once). Workspace: chunk_sumsq (double[nchunks]),
+// chunk_bad (int[nchunks]), bad (int[T]); scalars: float[2] out (total norm, clip coef).
+int mvae_multi_tensor_adam(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int* chunk_tensor,
+                           const long long* chunk_start, const int* chunk_len, int nchunks,
+                           const int* tensor_chunk_begin, int ntensors, const int* used, int* step, float grad_scale,
+                           float max_norm, int do_clip, double lr, double beta1, double beta2, float eps,
+                           double weight_decay, int decoupled, void* workspace, size_t workspace_bytes, float* scalars,
+                           void* stream) {
+  return mt_adam_launch(params, grads, exp_avg, exp_avg_sq, chunk_tensor, chunk_start, chunk_len, nchunks,
+                        tensor_chunk_begin, ntensors, used, step, grad_scale, max_norm, do_clip, lr, beta1, beta2, eps,
+                        weight_decay, decoupled, workspace, workspace_bytes, scalars, nullptr, 0.0, stream);
+}
+
+// The same step, also averaging the weights: ema (laid out like params) = ema * ema_decay + (1 - ema_decay) * params
+// after the update, for every tensor (used or not). params, grads, moments, step and scalars come out as above.
+int mvae_multi_tensor_adam_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const int* chunk_tensor,
+                               const long long* chunk_start, const int* chunk_len, int nchunks,
+                               const int* tensor_chunk_begin, int ntensors, const int* used, int* step,
+                               float grad_scale, float max_norm, int do_clip, double lr, double beta1, double beta2,
+                               float eps, double weight_decay, int decoupled, void* workspace, size_t workspace_bytes,
+                               float* scalars, float* ema, double ema_decay, void* stream) {
+  if (!ema) { set_error("adam_ema: null ema buffer"); return MVAE_EINVAL; }
+  if (!(ema_decay >= 0.0 && ema_decay < 1.0)) { set_error("adam_ema: ema_decay must be in [0, 1)"); return MVAE_EINVAL; }
+  return mt_adam_launch(params, grads, exp_avg, exp_avg_sq, chunk_tensor, chunk_start, chunk_len, nchunks,
+                        tensor_chunk_begin, ntensors, used, step, grad_scale, max_norm, do_clip, lr, beta1, beta2, eps,
+                        weight_decay, decoupled, workspace, workspace_bytes, scalars, ema, ema_decay, stream);
+}
+
+// Exchange two device buffers of n floats in place (no temporary).
+int mvae_swap_buffers(float* a, float* b, size_t n, void* stream) {
+  if (!a || !b || n == 0) { set_error("swap_buffers: null pointer or empty"); return MVAE_EINVAL; }
+  if (a == b) return MVAE_OK;
+  const int vec = (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+  const size_t groups = (n + 1023) / 1024;  // 256 threads x 4 floats
+  const int blocks = (int)(groups < 2048 ? groups : 2048);
+  hipLaunchKernelGGL(swap_buffers_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, n, vec);
   return launch_status();
 }
 

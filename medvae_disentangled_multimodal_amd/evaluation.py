@@ -7,6 +7,7 @@ no host synchronisation, the aggregation runs on the device, and one device-to-h
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 from typing import Any, Dict, Iterable, Optional, Tuple
@@ -21,7 +22,7 @@ LATENT_KEYS = ("latent_mean_avg", "latent_std_avg", "latent_sparsity")
 
 
 def evaluate_model(module, batches: Iterable, num_batches: Optional[int] = None, output_dir: Optional[str] = None,
-                   keep_latents: int = 1000) -> Tuple[Dict[str, Any], Dict[str, Optional[torch.Tensor]]]:
+                   keep_latents: int = 1000, use_ema: bool = False) -> Tuple[Dict[str, Any], Dict[str, Optional[torch.Tensor]]]:
     """Run `module` (a VAELightningModule) over `batches` of device tensors -- (x, labels), (x, labels, modality) or
     (x, labels, modality, modality_indices), dispatched like validation_step -- in eval mode, without autograd and in
     the module's precision. At most `num_batches` batches are read (default: len(batches)).
@@ -34,6 +35,8 @@ def evaluate_model(module, batches: Iterable, num_batches: Optional[int] = None,
       collected = {"latents", "labels", "modalities"}: the first `keep_latents` samples' z, labels and modality
                   vectors as host tensors (what the reference hands to its latent-space plot); "modalities" is None
                   for batches without one.
+    use_ema: evaluate the exponential moving average of the weights (optimizer_config["ema_decay"]): the loop runs
+    inside module.ema_scope(), which puts the live weights back on every exit path.
     The model's train / eval state and the math mode are restored on every exit path."""
     if num_batches is None:
         if not hasattr(batches, "__len__"):
@@ -50,7 +53,7 @@ def evaluate_model(module, batches: Iterable, num_batches: Optional[int] = None,
     module.model.eval()
     prev = ops.set_precision(module.precision)
     try:
-        with torch.no_grad():
+        with torch.no_grad(), (module.ema_scope() if use_ema else contextlib.nullcontext()):
             for i, batch in enumerate(batches):
                 if i >= num_batches:
                     break

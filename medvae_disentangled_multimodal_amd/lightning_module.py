@@ -16,9 +16,14 @@ window of N: the flat gradient is zeroed and the weight formats are prepared on 
 backward adds its gradient into the flat slots, and on the window's last micro-batch the exchange runs, the sum is
 divided by N (the gradient of Lightning's loss / N) and non-finite zeroing, clip and Adam/AdamW run once (DESIGN
 section 13).
+
+`optimizer_config["ema_decay"]` (absent or None: off) keeps an exponential moving average of the model's weights, updated
+once per optimizer step inside the fused Adam kernel (optim.FusedAdam.ema); `ema_scope()` puts the averaged weights under
+the model for evaluation or sampling, and `evaluate(..., use_ema=True)` validates with them.
 """
 from __future__ import annotations
 
+import contextlib
 import inspect
 import os
 from typing import Any, Dict, Optional, Tuple
@@ -29,7 +34,7 @@ import torch.nn as nn
 from .disentangled import DisentangledConditionalVAE
 from . import ops
 from .losses import DisentangledVAELoss, LPIPSLoss, LPIPSWithDiscriminator, VAELoss
-from .optim import Adam, AdamW, FlatParameters, FusedAdam
+from .optim import Adam, AdamW, FlatParameters, FusedAdam, check_ema_decay
 from .schedulers import get_scheduler
 
 try:  # Lightning is optional: the module works stand-alone
@@ -98,6 +103,8 @@ class VAELightningModule(_Base):
         self.global_step_count = 0
         self.model = model
         self.optimizer_config = dict(optimizer_config)
+        check_ema_decay(self.optimizer_config.get("ema_decay"))  # (refused here, not at the first step)
+        self._in_ema_scope = False
         self.scheduler_config = dict(scheduler_config or {"type": "none"})
         self.loss_config = dict(loss_config)
         self.gradient_clip_val = gradient_clip_val
@@ -255,18 +262,49 @@ class VAELightningModule(_Base):
         return self._eval_step(batch, "test")
 
     @torch.no_grad()
-    def evaluate(self, batch, split: str = "val"):
+    def evaluate(self, batch, split: str = "val", use_ema: bool = False):
         """Stand-alone validation of one batch (what Lightning's loop does around validation_step):
-        eval mode, no autograd, the configured precision; returns the logged `{split}/*` tensors."""
+        eval mode, no autograd, the configured precision; returns the logged `{split}/*` tensors.
+        use_ema: with the averaged weights under the model (ema_scope)."""
         was_training = self.model.training
         self.model.eval()
         prev = ops.set_precision(self.precision)
         try:
-            self._eval_step(batch, split)
+            with self.ema_scope() if use_ema else contextlib.nullcontext():
+                self._eval_step(batch, split)
         finally:
             ops.restore_math_mode(prev)
             self.model.train(was_training)
         return {k: v for k, v in self.logged.items() if k.startswith(f"{split}/")}
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Inside the scope the model's parameters hold the averaged weights (optimizer_config["ema_decay"]); the live
+        weights come back on every exit path. The two flat buffers are exchanged in place (FusedAdam.swap_ema: no copy
+        of the 3.7 GB a c4 model's weights take), and the step's prepared weight formats are marked stale both ways, so
+        every convolution inside the scope converts the weight it finds in the flat buffer, and the next training step
+        prepares the live ones again. No optimisation step may run inside (it would update the average as the weights
+        and the weights as the average): fit_step / fit_step_graphed raise, as does entering with an accumulation
+        window open (its gradients belong to the live weights) or a second time."""
+        opt = self.optimizer
+        if opt is None or getattr(opt, "ema", None) is None:
+            raise RuntimeError('ema_scope: EMA is not enabled (set optimizer_config["ema_decay"] and call '
+                               "configure_optimizers or fit_step first)")
+        if self.accumulating:
+            raise RuntimeError("ema_scope: a gradient-accumulation window is open; enter at a step boundary")
+        if self._in_ema_scope:
+            raise RuntimeError("ema_scope: already inside the scope")
+        opt.swap_ema()
+        self._in_ema_scope = True
+        try:
+            yield self
+        finally:
+            self._in_ema_scope = False
+            opt.swap_ema()
+
+    def _refuse_in_ema_scope(self, what: str):
+        if self._in_ema_scope:
+            raise RuntimeError(f"{what}: called inside ema_scope() (the model holds the averaged weights)")
 
     # ---------------------------------------------------------------------------------------
     def teardown(self, stage: Optional[str] = None):
@@ -276,16 +314,18 @@ class VAELightningModule(_Base):
         ops.release_weight_buffers()
 
     def configure_optimizers(self):
+        self._refuse_in_ema_scope("configure_optimizers")
         self._graph = None  # a captured step holds the previous optimizer's buffers and hyper-parameters
         ops.release_weight_buffers()  # (rebuilt by the next prepared step, for this optimizer's flat buffer)
         if self.flat is None:
             self.flat = FlatParameters(self.model)
         oc = self.optimizer_config
         betas = tuple(oc.get("betas", (0.9, 0.999)))
+        ema = oc.get("ema_decay")  # (the generator's optimizer only: the discriminator is not averaged)
         if oc["type"] == "adam":
-            opt = Adam(self.flat, lr=oc["lr"], betas=betas, weight_decay=oc.get("weight_decay", 0))
+            opt = Adam(self.flat, lr=oc["lr"], betas=betas, weight_decay=oc.get("weight_decay", 0), ema_decay=ema)
         elif oc["type"] == "adamw":
-            opt = AdamW(self.flat, lr=oc["lr"], betas=betas, weight_decay=oc.get("weight_decay", 1e-4))
+            opt = AdamW(self.flat, lr=oc["lr"], betas=betas, weight_decay=oc.get("weight_decay", 1e-4), ema_decay=ema)
         else:
             raise ValueError(f"Unknown optimizer: {oc['type']}")
         opt.max_grad_norm = self.gradient_clip_val
@@ -357,6 +397,7 @@ class VAELightningModule(_Base):
         and the usage mask run eagerly between the last micro-batch's replay and the optimizer's, as in "split". A window is
         replayed only from its first micro-batch on: one opened eagerly (or met by a re-capture) finishes eagerly,
         because the later-micro-batch piece reads the weight formats the first piece's replay prepared."""
+        self._refuse_in_ema_scope("fit_step_graphed")
         if self.use_discriminator:
             raise RuntimeError("fit_step_graphed: adversarial steps run eagerly (fit_step)")
         if self.optimizer is None or self.global_step_count == 0:
@@ -624,6 +665,7 @@ class VAELightningModule(_Base):
         a whole optimisation step; with N > 1 the optimizer steps on every N-th call, or on a call flagged last_batch
         (the epoch's last micro-batch closes the window early; its gradient is still divided by N, as in Lightning).
         Returns the undivided loss, detached."""
+        self._refuse_in_ema_scope("fit_step")
         if self.optimizer is None:
             self.configure_optimizers()
         if self.use_discriminator and self.global_step_count >= self.criterion.discriminator_iter_start:

@@ -96,13 +96,26 @@ class FlatParameters:
         return self.names.index(name)
 
 
+def check_ema_decay(ema_decay) -> Optional[float]:
+    """None (no average) or the decay as a float; anything outside 0 <= decay < 1 is refused."""
+    if ema_decay is None:
+        return None
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"ema_decay must be a number in [0, 1) or None, got {ema_decay!r}")
+    return float(ema_decay)
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam / AdamW semantics over a FlatParameters buffer in one fused kernel chain.
     `step()` also applies the LightningModule hooks that precede it in the reference:
     per-tensor non-finite zeroing (on_before_optimizer_step) and global-norm clipping."""
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 decoupled: bool = False, max_grad_norm: Optional[float] = None):
+                 decoupled: bool = False, max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None):
+        """ema_decay: keep an exponential moving average of the weights, `self.ema` (a flat fp32 buffer laid out like
+        flat.data, starting as its copy), updated inside the step's Adam kernel: ema = ema * decay + (1 - decay) * p
+        for every parameter after each step (the reference's exponential_moving_average helper). None: no average."""
+        ema_decay = check_ema_decay(ema_decay)
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         super().__init__(flat.params, defaults)
         self.flat = flat
@@ -114,6 +127,8 @@ class FusedAdam(torch.optim.Optimizer):
         self.steps = torch.zeros(len(flat.params), dtype=torch.int32, device=dev)
         self.scalars = torch.zeros(2, device=dev, dtype=torch.float32)
         self.grad_scale = 1.0
+        self.ema_decay = ema_decay
+        self.ema = flat.data.detach().clone() if ema_decay is not None else None  # (the padding stays zero)
 
     @property
     def last_total_norm(self) -> torch.Tensor:
@@ -133,30 +148,55 @@ class FusedAdam(torch.optim.Optimizer):
         clip = self.max_grad_norm
         st = torch.cuda.current_stream(f.device).cuda_stream
         b1, b2 = g["betas"]
-        _lib.call("mvae_multi_tensor_adam", f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
-                  self.exp_avg_sq.data_ptr(), f.chunk_tensor.data_ptr(), f.chunk_start.data_ptr(),
-                  f.chunk_len.data_ptr(), f.nchunks, f.tensor_chunk_begin.data_ptr(), len(f.params),
-                  used.data_ptr(), self.steps.data_ptr(), float(self.grad_scale),
-                  float(clip) if clip else 0.0, 1 if (clip is not None and clip > 0) else 0, float(g["lr"]),
-                  float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), 1 if self.decoupled else 0,
-                  ws.data_ptr(), ws.numel(), self.scalars.data_ptr(), st)
+        args = (f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
+                self.exp_avg_sq.data_ptr(), f.chunk_tensor.data_ptr(), f.chunk_start.data_ptr(),
+                f.chunk_len.data_ptr(), f.nchunks, f.tensor_chunk_begin.data_ptr(), len(f.params),
+                used.data_ptr(), self.steps.data_ptr(), float(self.grad_scale),
+                float(clip) if clip else 0.0, 1 if (clip is not None and clip > 0) else 0, float(g["lr"]),
+                float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), 1 if self.decoupled else 0,
+                ws.data_ptr(), ws.numel(), self.scalars.data_ptr())
+        if self.ema is None:
+            _lib.call("mvae_multi_tensor_adam", *args, st)
+        else:  # the same launches, the Adam kernel also averaging the weights
+            _lib.call("mvae_multi_tensor_adam_ema", *args, self.ema.data_ptr(), self.ema_decay, st)
         return loss
 
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the weights and their average in place (no temporary copy of the flat buffer): the model's
+        parameters, views of flat.data, then hold the averaged weights and `self.ema` the live ones, until the next
+        call swaps them back. The prepared weight formats of the step are marked stale."""
+        if self.ema is None:
+            raise RuntimeError("swap_ema: this optimizer keeps no EMA (ema_decay is None)")
+        f = self.flat
+        _lib.call("mvae_swap_buffers", f.data.data_ptr(), self.ema.data_ptr(), f.numel,
+                  torch.cuda.current_stream(f.device).cuda_stream)
+        from . import ops
+        ops.flat_weights_stale()
+
     def state_dict(self):
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "steps": self.steps,
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        sd = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "steps": self.steps,
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        if self.ema is not None:
+            sd["ema"] = self.ema
+        return sd
 
     def load_state_dict(self, sd):
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.steps.copy_(sd["steps"])
+        if self.ema is not None:
+            # (a state without an average, e.g. of a run that kept none: the average restarts from the weights)
+            self.ema.copy_(sd["ema"] if "ema" in sd else self.flat.data)
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
 
 
-def AdamW(flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
-    return FusedAdam(flat, lr, betas, eps, weight_decay, decoupled=True, max_grad_norm=max_grad_norm)
+def AdamW(flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_decay=None):
+    return FusedAdam(flat, lr, betas, eps, weight_decay, decoupled=True, max_grad_norm=max_grad_norm,
+                     ema_decay=ema_decay)
 
 
-def Adam(flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
-    return FusedAdam(flat, lr, betas, eps, weight_decay, decoupled=False, max_grad_norm=max_grad_norm)
+def Adam(flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
+    return FusedAdam(flat, lr, betas, eps, weight_decay, decoupled=False, max_grad_norm=max_grad_norm,
+                     ema_decay=ema_decay)
