@@ -329,125 +329,169 @@ struct WinoOut {
   int nb, H, W, N;
 };
 
-// M -> y = A^T M A (+ bias) (+ residual). A thread covers whole 32-pixel blocks of the statistics layouts: TR tile rows
-// x CT tiles of one image, i.e. an (TR m) x WSEG pixel window with WSEG = min(W, 32) (W in {8, 16}: the full width, TR
-// = 32 / (m W) tile rows when that is > 1; W a multiple of 32: one tile row of a 32-pixel column segment) -- NBK = TR m
-// WSEG / 32 blocks, each block's sums in registers (compile-time index). Threads of a group are consecutive 4-channel
-// groups (coalesced 16-B loads / stores).
+// M -> y = A^T M A (+ bias) (+ residual). One thread per (tile, 4-channel group), as the input transform: every load of
+// the thread -- the a^2 M groups and the m^2 residual (or GroupNorm-input) groups -- issues before any arithmetic, and
+// the grid is one wave-slot per tile instead of one per window. A workgroup covers whole 32-pixel blocks of the
+// statistics layouts: the TW = TR x CT tiles of an (TR m) x WSEG pixel window of one image, WSEG = min(W, 32) (W in
+// {8, 16}: the full width, TR = 32 / (m W) tile rows when that is > 1; W a multiple of 32: one tile row of a 32-pixel
+// column segment), by CG = 256 / TW consecutive 4-channel groups (coalesced 16-B loads / stores in runs of CG x 16 B).
+// A thread sums its tile's m pixel rows; the NBK = TR m WSEG / 32 blocks of the window are then summed over the
+// window's tiles through LDS in a fixed order (no atomics: repeatable bit for bit).
 template <int MT, int WSEG>
 struct WinoOutGeo {
   static constexpr int TR = MT * WSEG >= 32 ? 1 : 32 / (MT * WSEG);
   static constexpr int CT = WSEG / MT;
   static constexpr int NBK = TR * MT * WSEG / 32;
+  static constexpr int TW = TR * CT;     // tiles of a window
+  static constexpr int CG = 256 / TW;    // 4-channel groups of a workgroup
+  static constexpr int RPB = 32 / WSEG;  // pixel rows of a block
+  static_assert(TW * CG == 256 && NBK * CG <= 256 && NBK * RPB == TR * MT, "window geometry");
 };
+
+template <int MT, int WSEG>
+static long long wino_out_blocks(const WinoOut& p) {  // workgroups: windows x chunks of CG channel groups
+  using Geo = WinoOutGeo<MT, WSEG>;
+  return (long long)p.nb * (p.H / MT / Geo::TR) * (p.W / WSEG) * ((p.N / 4 + Geo::CG - 1) / Geo::CG);
+}
 
 template <int MT, int WSEG, bool GNB, bool ST>
 __global__ void __launch_bounds__(256) wino_out_kernel(WinoOut p) {
   constexpr int AL = MT + 2;
   using Geo = WinoOutGeo<MT, WSEG>;
-  constexpr int TR = Geo::TR, CT = Geo::CT, NBK = Geo::NBK;
+  constexpr int TR = Geo::TR, CT = Geo::CT, NBK = Geo::NBK, TW = Geo::TW, CG = Geo::CG, RPB = Geo::RPB;
   const int N = p.N, N4 = N >> 2, th = p.H / MT, tw = p.W / MT, nseg = p.W / WSEG;
+  const int nchunk = (N4 + CG - 1) / CG;
   const long long T = (long long)p.nb * th * tw;
   const unsigned mplane = (unsigned)(T * N4 * 16);
   const __amdgpu_buffer_rsrc_t mr = make_rsrc(p.m, mplane * (unsigned)(AL * AL));
-  const long long ngrp = (long long)p.nb * (th / TR) * nseg;
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= ngrp * N4) return;
-  const long long grp = idx / N4;
-  const int c4 = (int)(idx - grp * N4);
+  const int chunk = (int)(blockIdx.x % (unsigned)nchunk);
+  const long long grp = blockIdx.x / (unsigned)nchunk;
+  const int cl = threadIdx.x % CG, wt = threadIdx.x / CG;  // channel group of the chunk, tile of the window
+  // (a chunk's lanes past N / 4 run on the last channel group, so every load stays in range, and store nothing)
+  const bool act = chunk * CG + cl < N4;
+  const int c4 = act ? chunk * CG + cl : N4 - 1;
   const int seg = (int)(grp % nseg);
   const long long rg = grp / nseg;
   const int b = (int)(rg / (th / TR)), ti0 = (int)(rg % (th / TR)) * TR, tj0 = seg * CT;
-  const float4 bv = p.bias ? *(const float4*)(p.bias + c4 * 4) : float4{0.f, 0.f, 0.f, 0.f};
+  const int ti = ti0 + wt / CT, tj = tj0 + wt % CT;
   // y / residual / GroupNorm input through buffer descriptors (32-bit offsets; a null residual is an empty range,
   // whose loads return zeros: no branch and no wait per pixel)
   const unsigned ybytes = (unsigned)((long long)p.nb * p.H * p.W * N * 4);
   const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y, ybytes);
-  const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.res ? p.res : p.y, p.res ? ybytes : 0u);
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(GNB ? p.gx : p.y, GNB ? ybytes : 0u);
-  // (the GroupNorm-backward partials of one 32-pixel block are summed in fp32 -- 32 terms -- and stored as fp64: half
-  // the accumulator registers of fp64 sums, which with the full M tile in registers held this variant to one wave per
-  // SIMD)
-  double s0[NBK], s1[NBK];
-  float g0[GNB ? NBK : 1][4], g1[GNB ? NBK : 1][4];
+  const __amdgpu_buffer_rsrc_t er = GNB ? make_rsrc(p.gx, ybytes) : make_rsrc(p.res ? p.res : p.y, p.res ? ybytes : 0u);
+  const unsigned ybase = ((unsigned)((b * p.H + ti * MT) * p.W + tj * MT) * (unsigned)N + (unsigned)c4 * 4u) * 4u;
+  const unsigned yrow = (unsigned)p.W * (unsigned)N * 4u, ypix = (unsigned)N * 4u;
+  // the tile's second operand first (residual, or the GroupNorm input of the partials), then M one column at a time
+  // (A^T M consumes it by columns): all m^2 + a^2 loads are in flight before the first wait
+  float4 ev[MT][MT], mv[AL][AL];
 #pragma unroll
-  for (int q = 0; q < NBK; ++q) s0[q] = s1[q] = 0.0;
+  for (int a = 0; a < MT; ++a)
 #pragma unroll
-  for (int q = 0; q < (GNB ? NBK : 1); ++q)
+    for (int e = 0; e < MT; ++e) ev[a][e] = bload4(er, ybase + (unsigned)a * yrow + (unsigned)e * ypix);
+  const long long t = ((long long)b * th + ti) * tw + tj;
+  const unsigned mbase = (unsigned)(t * N4 + c4) * 16u;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) g0[q][u] = g1[q][u] = 0.f;
-  float ggm[4] = {0.f, 0.f, 0.f, 0.f}, gbt[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < AL; ++j)
+#pragma unroll
+    for (int i = 0; i < AL; ++i) mv[i][j] = bload4(mr, mbase + (unsigned)(i * AL + j) * mplane);
+  const float4 bv = p.bias ? *(const float4*)(p.bias + c4 * 4) : float4{0.f, 0.f, 0.f, 0.f};
+  float ggm[4] = {0.f, 0.f, 0.f, 0.f}, gbt[4] = {0.f, 0.f, 0.f, 0.f}, mu = 0.f, rs = 0.f;
   if constexpr (GNB) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       ggm[e] = p.gamma[c4 * 4 + e];
       gbt[e] = p.beta[c4 * 4 + e];
     }
+    const int bg = b * p.groups + (c4 * 4) / (N / p.groups);  // (a 4-channel group never straddles a GroupNorm group)
+    mu = p.mean[bg];
+    rs = p.rstd[bg];
   }
-  const int cpg = GNB ? N / p.groups : 1;
   const bool silu = GNB && p.silu != 0;
+  // per pixel row of the tile: {sum y, sum y^2} of the 4 channels (fp64), or per channel {sum dyn, sum dyn * xhat}
+  // (fp32 over the row's m pixels; the block sum below runs in fp64)
+  double s0[ST ? MT : 1], s1[ST ? MT : 1];
+  float g0[GNB ? MT : 1][4], g1[GNB ? MT : 1][4];
+  constexpr auto at = [](int i, int k) { return wino_at<MT>(i, k); };
+  float4 r[MT][AL];
 #pragma unroll
-  for (int tr = 0; tr < TR; ++tr)
-#pragma unroll 1
-    for (int tq = 0; tq < CT; ++tq) {
-      const int ti = ti0 + tr, tj = tj0 + tq;
-      const long long t = ((long long)b * th + ti) * tw + tj;
-      const unsigned mbase = (unsigned)(t * N4 + c4) * 16u;
-      constexpr auto at = [](int i, int k) { return wino_at<MT>(i, k); };
-      float4 r[MT][AL];
-      float4 mv[AL][AL];
+  for (int j = 0; j < AL; ++j) wlin<MT, AL>(&r[0][j], AL, &mv[0][j], AL, at);  // A^T M
 #pragma unroll
-      for (int i = 0; i < AL; ++i)
+  for (int a = 0; a < MT; ++a) {
+    float4 o[MT];
+    wlin<MT, AL>(o, 1, &r[a][0], 1, at);  // (A^T M) A
+    if constexpr (ST) s0[a] = s1[a] = 0.0;
+    if constexpr (GNB) {
 #pragma unroll
-        for (int j = 0; j < AL; ++j) mv[i][j] = bload4(mr, mbase + (unsigned)(i * AL + j) * mplane);
+      for (int u = 0; u < 4; ++u) g0[a][u] = g1[a][u] = 0.f;
+    }
 #pragma unroll
-      for (int j = 0; j < AL; ++j) wlin<MT, AL>(&r[0][j], AL, &mv[0][j], AL, at);  // A^T M
+    for (int e = 0; e < MT; ++e) {
+      // (the input-gradient transform with GroupNorm partials has no bias / residual: mvae_winograd_output_gnbwd)
+      const float4 val = GNB ? o[e] : f4add(f4add(o[e], bv), ev[a][e]);
+      bstore4(yr, act ? ybase + (unsigned)a * yrow + (unsigned)e * ypix : OOB, val);
+      if constexpr (ST) {
+        s0[a] += ((double)val.x + (double)val.y) + ((double)val.z + (double)val.w);
+        s1[a] += ((double)val.x * val.x + (double)val.y * val.y) + ((double)val.z * val.z + (double)val.w * val.w);
+      }
+      if constexpr (GNB) {
+        const float xs[4] = {ev[a][e].x, ev[a][e].y, ev[a][e].z, ev[a][e].w}, vs[4] = {val.x, val.y, val.z, val.w};
 #pragma unroll
-      for (int a = 0; a < MT; ++a) {
-        float4 o[MT];
-        wlin<MT, AL>(o, 1, &r[a][0], 1, at);  // (A^T M) A
-        const int row = ti * MT + a;
-        const int q = ((tr * MT + a) * WSEG) / 32;  // block within the group (compile-time: tr, a unrolled)
-#pragma unroll
-        for (int e = 0; e < MT; ++e) {
-          const unsigned off = ((unsigned)((b * p.H + row) * p.W + tj * MT + e) * (unsigned)N + (unsigned)c4 * 4u) * 4u;
-          // (the input-gradient transform with GroupNorm partials has no bias / residual: mvae_winograd_output_gnbwd)
-          float4 val = GNB ? o[e] : f4add(f4add(o[e], bv), bload4(rr, off));
-          bstore4(yr, off, val);
-          if constexpr (ST) {
-            s0[q] += ((double)val.x + (double)val.y) + ((double)val.z + (double)val.w);
-            s1[q] += ((double)val.x * val.x + (double)val.y * val.y) + ((double)val.z * val.z + (double)val.w * val.w);
-          }
-          if constexpr (GNB) {
-            const float4 x4 = bload4(xr, off);
-            const int bg = b * p.groups + (c4 * 4) / cpg;  // (a 4-channel group never straddles a GroupNorm group)
-            const float mu = p.mean[bg], rs = p.rstd[bg];
-            const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, vs[4] = {val.x, val.y, val.z, val.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              float d = vs[u];
-              const float xh = (xs[u] - mu) * rs;
-              // (branch-free: a per-element branch on the uniform silu flag held this variant to one wave per SIMD)
-              const float yn = xh * ggm[u] + gbt[u];
-              const float sg = sigmoid_f(yn);
-              const float ds = d * sg * (1.f + yn * (1.f - sg));
-              d = silu ? ds : d;
-              g0[q][u] += d;
-              g1[q][u] += d * xh;
-            }
-          }
+        for (int u = 0; u < 4; ++u) {
+          float d = vs[u];
+          const float xh = (xs[u] - mu) * rs;
+          // (branch-free: a per-element branch on the uniform silu flag splits the arithmetic per element)
+          const float yn = xh * ggm[u] + gbt[u];
+          const float sg = sigmoid_f(yn);
+          const float ds = d * sg * (1.f + yn * (1.f - sg));
+          d = silu ? ds : d;
+          g0[a][u] += d;
+          g1[a][u] += d * xh;
         }
       }
     }
+  }
+  // block sums: window pixel row wr = tr m + a belongs to block wr / RPB; block q is summed over its rows, and each
+  // row over the window's CT tiles, in that order
+  if constexpr (ST) {
+    __shared__ double2 sm[TW][MT][CG];
 #pragma unroll
-  for (int q = 0; q < NBK; ++q) {
-    // first pixel of local block q: (q 32 / WSEG) rows down, at the group's column segment
-    const long long blk = (((long long)b * p.H + ti0 * MT + (q * 32) / WSEG) * p.W + seg * WSEG) >> 5;
-    if constexpr (ST) *(double2*)(p.gn_part + (blk * N4 + c4) * 2) = double2{s0[q], s1[q]};
-    if constexpr (GNB) {
-      double* gp = p.gnb_part + (blk * N + c4 * 4) * 2;
+    for (int a = 0; a < MT; ++a) sm[wt][a][cl] = double2{s0[a], s1[a]};
+    __syncthreads();
+    const int q = threadIdx.x / CG, cb = chunk * CG + cl;  // (cl: threadIdx.x % CG)
+    if (q < NBK && cb < N4) {
+      double2 s = double2{0.0, 0.0};
+      for (int wr = q * RPB; wr < (q + 1) * RPB; ++wr)
 #pragma unroll
-      for (int u = 0; u < 4; ++u) *(double2*)(gp + 2 * u) = double2{(double)g0[q][u], (double)g1[q][u]};
+        for (int tq = 0; tq < CT; ++tq) {
+          const double2 v = sm[(wr / MT) * CT + tq][wr % MT][cl];
+          s.x += v.x;
+          s.y += v.y;
+        }
+      // first pixel of block q: q RPB rows down the window, at the window's column segment
+      const long long blk = (((long long)b * p.H + ti0 * MT + q * RPB) * p.W + seg * WSEG) >> 5;
+      *(double2*)(p.gn_part + (blk * N4 + cb) * 2) = s;
+    }
+  }
+  if constexpr (GNB) {
+    __shared__ float2 sg[TW][MT][CG][4];
+#pragma unroll
+    for (int a = 0; a < MT; ++a)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) sg[wt][a][cl][u] = float2{g0[a][u], g1[a][u]};
+    __syncthreads();
+    for (int i = threadIdx.x; i < NBK * CG * 4; i += 256) {
+      const int u = i & 3, cc = (i >> 2) % CG, q = i / (4 * CG), cb = chunk * CG + cc;
+      if (cb >= N4) continue;
+      double d0 = 0.0, d1 = 0.0;
+      for (int wr = q * RPB; wr < (q + 1) * RPB; ++wr)
+#pragma unroll
+        for (int tq = 0; tq < CT; ++tq) {
+          const float2 v = sg[(wr / MT) * CT + tq][wr % MT][cc][u];
+          d0 += (double)v.x;
+          d1 += (double)v.y;
+        }
+      const long long blk = (((long long)b * p.H + ti0 * MT + q * RPB) * p.W + seg * WSEG) >> 5;
+      *(double2*)(p.gnb_part + (blk * N + cb * 4 + u) * 2) = double2{d0, d1};
     }
   }
 }
@@ -853,9 +897,7 @@ static void dy_go(const float* dy, void* v, void* d, int nb, int h, int w, int k
 
 template <int MT, int WSEG>
 static void wino_out_go(WinoOut& p, bool gnb, hipStream_t st) {
-  using Geo = WinoOutGeo<MT, WSEG>;
-  const long long groups = (long long)p.nb * (p.H / MT / Geo::TR) * (p.W / WSEG);
-  const dim3 g(egrid256(groups * (p.N / 4)));
+  const dim3 g((unsigned)wino_out_blocks<MT, WSEG>(p));
   if (gnb) hipLaunchKernelGGL((wino_out_kernel<MT, WSEG, true, false>), g, dim3(256), 0, st, p);
   else if (p.gn_part) hipLaunchKernelGGL((wino_out_kernel<MT, WSEG, false, true>), g, dim3(256), 0, st, p);
   else hipLaunchKernelGGL((wino_out_kernel<MT, WSEG, false, false>), g, dim3(256), 0, st, p);

@@ -3,7 +3,9 @@
 transforms against the HBM roofline (algorithmic bytes: every operand read once, every output written once), the
 position GEMMs in executed TF/s.
 usage: tools/wino_bench.py [reps] [tile]
-env WB_SHAPES=i,j (indices into SHAPES) and WB_STAGES=gemm,wgemm restrict the run (PMC passes over one kernel);
+env WB_SHAPES=i,j (indices into SHAPES) and WB_STAGES=gemm,wgemm restrict the run (PMC passes over one kernel); the
+output transform's variants are the stages out (plain), out_st / out_st_res (GroupNorm statistics, without / with a
+residual), out_gnb (input gradient with GroupNorm-backward partials) and out_ups (the Upsample conv's class images);
 WB_PREC=32-exact times the exact-fp32 arithmetic (bit-split operands, f32-input MFMA); WB_LIB=1 adds torch.bmm on the
 position GEMM's shape in the arithmetic's library dtype (fp32 for 32 / 32-exact: the hipBLASLt rate on the same batched
 short-K problem)."""
@@ -54,6 +56,21 @@ for nb, h, w, ci, co in SHAPES:
     sc = torch.rand(nb, ci, device=dev) + 0.5  # GroupNorm scale / shift rows (input transform with GroupNorm+SiLU)
     sh = torch.randn(nb, ci, device=dev) * 0.1
     ws = torch.empty(_lib.query("mvae_gemm_workspace_bytes", co, ci, t, POS), dtype=torch.uint8, device=dev)
+    # output-transform variants: GroupNorm statistics (fp64 pairs per 32-pixel block and 4-channel group), with and
+    # without a residual; the input gradient with GroupNorm-backward partials (fp64 pairs per block and channel; reads
+    # the GroupNorm input x); the Upsample conv's four class images interleaved (M is 4x as wide: a quarter of the
+    # batch, so the same M bytes as `out`)
+    blocks = nb * h * w // 32
+    stat = torch.empty(blocks * (co // 4) * 2, dtype=torch.float64, device=dev)
+    gpart = torch.empty(blocks * co * 2, dtype=torch.float64, device=dev)
+    res = torch.randn(nb, h, w, co, device=dev)
+    gx = torch.randn(nb, h, w, co, device=dev)
+    mean, rstd = torch.randn(nb * 32, device=dev) * 0.1, torch.rand(nb * 32, device=dev) + 0.5
+    gam, bet = torch.rand(co, device=dev) + 0.5, torch.randn(co, device=dev) * 0.1
+    nbu = nb // 4
+    tu = (t // nb) * nbu
+    yu = torch.empty(nbu, 2 * h, 2 * w, co, device=dev)
+    m.normal_()
     stages = [
         ("wt_fwd", lambda: _lib.call("mvae_winograd_weight_transform", wt.data_ptr(), u.data_ptr(), ci, co, 0, MT, st),
          4.0 * co * ci * (9 + POS), 0),
@@ -67,6 +84,18 @@ for nb, h, w, ci, co in SHAPES:
          4.0 * POS * (t * ci + ci * co + t * co), 2.0 * POS * t * ci * co),
         ("out", lambda: _lib.call("mvae_winograd_output_transform", m.data_ptr(), None, None, y.data_ptr(), None, nb, h,
                                   w, co, MT, st), 4.0 * (POS * t * co + y.numel()), 0),
+        ("out_st", lambda: _lib.call("mvae_winograd_output_transform", m.data_ptr(), None, None, y.data_ptr(),
+                                     stat.data_ptr(), nb, h, w, co, MT, st),
+         4.0 * (POS * t * co + y.numel()) + 8.0 * stat.numel(), 0),
+        ("out_st_res", lambda: _lib.call("mvae_winograd_output_transform", m.data_ptr(), None, res.data_ptr(),
+                                         y.data_ptr(), stat.data_ptr(), nb, h, w, co, MT, st),
+         4.0 * (POS * t * co + 2 * y.numel()) + 8.0 * stat.numel(), 0),
+        ("out_gnb", lambda: _lib.call("mvae_winograd_output_gnbwd", m.data_ptr(), y.data_ptr(), gx.data_ptr(),
+                                      mean.data_ptr(), rstd.data_ptr(), gam.data_ptr(), bet.data_ptr(), 32, 1,
+                                      gpart.data_ptr(), nb, h, w, co, MT, st),
+         4.0 * (POS * t * co + 2 * y.numel()) + 8.0 * gpart.numel(), 0),
+        ("out_ups", lambda: _lib.call("mvae_winograd_output_transform_upsample", m.data_ptr(), None, yu.data_ptr(), nbu,
+                                      h, w, co, MT, st), 4.0 * (POS * tu * 4 * co + yu.numel()), 0),
         ("dy", lambda: _lib.call("mvae_winograd_dy_transform", dy.data_ptr(), d.data_ptr(), nb, h, w, co, 0, MT, st),
          4.0 * (dy.numel() + POS * t * co), 0),
         ("wgemm", lambda: _lib.call("mvae_winograd_wgrad_gemm", d.data_ptr(), v.data_ptr(), mw.data_ptr(), t, co, ci, MT,
@@ -83,11 +112,13 @@ for nb, h, w, ci, co in SHAPES:
     for name, fn, nbytes, flops in stages:
         if ONLY and name not in ONLY and not (name == "in" and "wgemm" in ONLY) and not (name == "dy" and "wgemm" in ONLY):
             continue
+        if name in ("out_st", "out_st_res", "out_gnb") and not (h % 4 == 0 and (w in (8, 16) or w % 32 == 0)):
+            continue  # (the statistics layouts need whole 32-pixel blocks: not on the c2 levels)
         us = timed(fn)
         tot[name] = tot.get(name, 0.0) + us
         rate = f"{flops / us / 1e6:6.1f}TF/s" if flops else f"{nbytes / us / 1e6:5.2f}TB/s"
         row.append(f"{name} {us:7.1f}us {rate}")
     print((nb, h, w, ci, co), " | ".join(row), flush=True)
-    del x, dy, y, wt, u, v, d, m, mw, dw, ws, sc, sh
+    del x, dy, y, wt, u, v, d, m, mw, dw, ws, sc, sh, stat, gpart, res, gx, yu
     torch.cuda.empty_cache()
 print("total us:", {k: round(v, 1) for k, v in tot.items()})
