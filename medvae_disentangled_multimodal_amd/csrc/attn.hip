@@ -30,7 +30,7 @@ struct AtTypes {
 // ds_read_b64_tr_b16 builtin so its own lgkmcnt waits cover them)
 template <bool COL>
 __device__ __forceinline__ bf16x8 at_frag(const __bf16* plane, int row0, int lane) {
-  return read_frag<64, COL, 16>(plane, row0, 0, lane);
+  return read_frag<64, COL>(plane, row0, lane);
 }
 
 // the 64 x 64 block A (M rows) x B (N rows) over g.K, both operands staged from HBM through the LDS images ia / ib

@@ -106,14 +106,14 @@ __global__ void __launch_bounds__(NT) conv_direct32_kernel(CdArgs a) {
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int off = (t / 3) * a.PW + (t % 3);  // output padded pixel p reads input padded pixel p + off
-        const bf16x8 ah = read_frag<MAXPIX, false, 16>(xs, mt * 16 + off, 0, lane);
+        const bf16x8 ah = read_frag<MAXPIX, false>(xs, mt * 16 + off, lane);
         bf16x8 al{};
-        if constexpr (PREC != 1) al = read_frag<MAXPIX, false, 16>(xs + PL, mt * 16 + off, 0, lane);
+        if constexpr (PREC != 1) al = read_frag<MAXPIX, false>(xs + PL, mt * 16 + off, lane);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const bf16x8 bh = read_frag<CD_C, false, 16>(ws + t * CD_C * CD_PITCH, j * 16, 0, lane);
+          const bf16x8 bh = read_frag<CD_C, false>(ws + t * CD_C * CD_PITCH, j * 16, lane);
           bf16x8 bl{};
-          if constexpr (PREC != 1) bl = read_frag<CD_C, false, 16>(ws + WPL + t * CD_C * CD_PITCH, j * 16, 0, lane);
+          if constexpr (PREC != 1) bl = read_frag<CD_C, false>(ws + WPL + t * CD_C * CD_PITCH, j * 16, lane);
           mma<PREC>(acc[j], ah, al, bh, bl);
         }
       }

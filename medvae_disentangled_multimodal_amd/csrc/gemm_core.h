@@ -55,10 +55,9 @@ constexpr int BK = 32;
 // MFMA shape per kernel (template MF): v_mfma_f32_16x16x32_bf16 (MF 16) or v_mfma_f32_32x32x16_bf16
 // (MF 32). Both take the same cycles per FLOP, but on random data the chip holds a higher clock under
 // the 16x16x32 loop: +8-11 % bf16 FLOP/s in this kernel's per-wave structure (tools/micro/mfma_shape.hip),
-// +3-5 % on the conv fwd/dgrad GEMMs. The wgrad / attention GEMMs, whose A operand is a transposed
-// (COL) image, measured 5-7 % faster with 32x32x16 and keep it (mf_of).
+// +3-5 % on the conv fwd/dgrad GEMMs. Every register-staged loop runs on 16x16x32 (one k-step per K-tile); only the
+// LDS-DMA loops of the weight gradient, whose operands are transposed (COL) images, run on 32x32x16 (MF in gemm3x_kernel).
 template <int MF> using acc_of = typename std::conditional<MF == 32, f32x16, f32x4>::type;
-template <int MF> constexpr int ks_of() { return BK / (MF == 32 ? 16 : 32); }  // MFMA k-steps per K-tile
 template <int MF> constexpr int nr_of() { return MF == 32 ? 16 : 4; }          // accumulator registers per tile
 // LDS swizzles, conflict-free for the fragment reads of both MFMA shapes:
 //  ROW image: 16-B k-chunk c of row r sits at chunk position c ^ row_swz(r) (the 16x16x32 ds_read_b128
@@ -229,30 +228,19 @@ __device__ __forceinline__ void st_presplit(__bf16* img, int plane, int off, con
     *(u32x2_t*)(img + plane + off) = u32x2_t{__float_as_uint(v.z), __float_as_uint(v.w)};
 }
 
-// MFMA operand fragment, k-step ks of the K-tile.
-//  32x32x16: lane l holds element [row0 + (l&31)][ks*16 + 8*(l>>5) + j]
-//  16x16x32: lane l holds element [row0 + (l&15)][8*(l>>4) + j]
-template <int ROWS, bool COL, int MF>
-__device__ __forceinline__ bf16x8 read_frag(const __bf16* plane, int row0, int ks, int lane) {
+// MFMA operand fragment of the K-tile's one 16x16x32 k-step: lane l holds element [row0 + (l&15)][8*(l>>4) + j].
+// (Every register-staged loop runs on 16x16x32 MFMAs; the 32x32x16 fragments of the DMA COL x COL loops are
+// dcfrag_asm's.)
+template <int ROWS, bool COL>
+__device__ __forceinline__ bf16x8 read_frag(const __bf16* plane, int row0, int lane) {
   if constexpr (!COL) {
-    if constexpr (MF == 32) {
-      const int r = row0 + (lane & 31);
-      return *(const bf16x8*)(plane + r * 40 + (((2 * ks + (lane >> 5)) ^ row_swz(r)) << 3));
-    } else {
-      const int r = row0 + (lane & 15);
-      return *(const bf16x8*)(plane + r * 40 + (((lane >> 4) ^ row_swz(r)) << 3));
-    }
+    const int r = row0 + (lane & 15);
+    return *(const bf16x8*)(plane + r * 40 + (((lane >> 4) ^ row_swz(r)) << 3));
   } else {
     constexpr int P = Img<ROWS, true>::PITCH;
     const int g = lane >> 4, li = lane & 15;
-    const __bf16* p;
-    if constexpr (MF == 32) {
-      const int kr = ks * 16 + (g >> 1) * 8 + (li >> 2);
-      p = plane + kr * P + ((row0 + (g & 1) * 16 + 4 * (li & 3)) ^ col_swz(kr));
-    } else {
-      const int kr = g * 8 + (li >> 2);
-      p = plane + kr * P + ((row0 + 4 * (li & 3)) ^ col_swz(kr));
-    }
+    const int kr = g * 8 + (li >> 2);
+    const __bf16* p = plane + kr * P + ((row0 + 4 * (li & 3)) ^ col_swz(kr));
     const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)p);
     const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(p + 4 * P));
     return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -289,12 +277,8 @@ __device__ __forceinline__ bool tap_src(const GemmArgs& a, int pt, int pl, int o
 // ds_write_b64 serves 16 lanes (2 rows) per LDS cycle; with the 80-B row pitch rows r and r+1 overlap
 // in 4 banks, rows r and r+4 are 16 banks apart -- so lane groups pair rows (0,4),(1,5),(2,6),(3,7).
 __device__ __forceinline__ int row_of_tid(int tid) {
-#ifdef MVAE_NO_ROW_SWIZZLE
-  return tid >> 3;
-#else
   const int g = (tid >> 3) & 7;
   return (tid >> 6) * 8 + ((g >> 1) | ((g & 1) << 2));
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -672,9 +656,6 @@ struct LoadWgradX {
     krw = (C4 % 64 == 0) ? __builtin_amdgcn_readfirstlane(kr) : kr;
   }
   __device__ void prep(const GemmArgs& a) {
-#ifdef MVAE_WGRAD_XFAKE  // timing-only build: no gather index math (wrong results)
-    return;
-#endif
     // slot 0's pixel by division; the others step from it (pixels NT / C4 apart: usually the same or the next image
     // row), so each K-tile costs one decomposition instead of NS -- the k-rows are wave-uniform, this is scalar work
     // on every wave of the workgroup, and the wgrad loop is short of scalar issue (PMC: 16 % of wave cycles in the
@@ -719,12 +700,6 @@ struct LoadWgradX {
     const unsigned img = (unsigned)(a.H * a.W);
     const int krow = kr + i * (NT / C4);
     const bool kv = (!KROW_CHECK || krow < BK) & (k + krow < a.K);
-#ifdef MVAE_WGRAD_XFAKE
-    if (VEC == 4) {
-      v[i] = bload4(rs, (kv & nv[0]) ? (unsigned)(((k + krow) * a.Cx + cc[0]) * 4) : OOB);
-      return;
-    }
-#endif
     if constexpr (FAST) {
       const bool ok = kv & nv[0] & ((unsigned)(sh[i] + rr[0]) < (unsigned)a.H) & ((unsigned)(sw[i] + ss[0]) < (unsigned)a.W);
       v[i] = bload4(rs, ok ? sbase[i] + ldelta : OOB);
@@ -841,9 +816,6 @@ struct LoadWgradXP2 {
 // [0,3,2,1][(r >> 2) & 3]).
 // ------------------------------------------------------------------------------------------
 constexpr int DBK = 64;  // split-K granularity (whole stages of either loop)
-#ifndef MVAE_DMA_SPREAD  // 1: COL (weight-gradient) loops spread their DMA issue over the k-steps; 2: every loop
-#define MVAE_DMA_SPREAD 1
-#endif
 template <int KT>
 __device__ __forceinline__ int dswz(int r) { return KT == 64 ? (r >> 1) & 7 : (4 - ((r >> 2) & 3)) & 3; }
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -1074,11 +1046,6 @@ struct DmaWgradX {
     for (int i = 0; i < S::NI; ++i) {
       const int kk = k + kr0 + i * S::NW * S::KPI;
       const int p = min(kk, K - 1);
-#ifdef MVAE_WGRAD_XFAKE  // timing-only build: no gather index math (wrong results)
-      ok_[i] = nv & (kk < K);
-      off_[i] = (unsigned)p * (unsigned)a.Cx * 2u + cb;
-      continue;
-#endif
       const int b = mdiv(p, a.mg_hw);
       const int rem = p - b * (a.Ho * a.Wo);
       const int oh = mdiv(rem, a.mg_wo);
@@ -1174,7 +1141,7 @@ __device__ __forceinline__ void wait_lgkm() {
 template <int KIND, int ROWS, int NT, bool IS_A, int KT>
 struct DmaLoader;
 template <int ROWS, int NT, bool IS_A, int KT>
-struct DmaLoader<0, ROWS, NT, IS_A, KT> : DmaRowK<ROWS, NT, IS_A, KT> {};
+struct DmaLoader<A_ROWK, ROWS, NT, IS_A, KT> : DmaRowK<ROWS, NT, IS_A, KT> {};
 template <int ROWS, int NT, int KT>
 struct DmaLoader<A_CONV_FWD, ROWS, NT, true, KT> : DmaConvA<ROWS, NT, MODE_FWD, KT> {};
 template <int ROWS, int NT, int KT>
@@ -1233,43 +1200,45 @@ __device__ __forceinline__ int acc_row(int r, int lane) {
   if constexpr (MF == 32) return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
   else return 4 * (lane >> 4) + r;
 }
-// MFMA shape of a kernel: 32x32x16 when A is a transposed (COL) image (wgrad, attention backward)
-constexpr int mf_of(int ak) { return (ak == A_COLM || ak == A_COLM_PIX || ak == A_COLM_SPLIT) ? 32 : 16; }
+// A is a transposed (COL) image: the weight gradients' dY^T, the attention backward's transposed operands
+constexpr bool a_is_col(int ak) { return ak == A_COLM || ak == A_COLM_PIX || ak == A_COLM_SPLIT; }
 
+// register-staged loaders by operand kind (the ROWK / COLM kinds serve either operand: A_ROWK == B_ROWK, A_COLM == B_COLN)
+static_assert((int)A_ROWK == (int)B_ROWK && (int)A_COLM == (int)B_COLN, "shared loader kinds");
 template <int KIND, int ROWS, int VEC, int NT, bool IS_A, int PREC>
 struct Loader;
 template <int ROWS, int VEC, int NT, bool IS_A, int PREC>
-struct Loader<0, ROWS, VEC, NT, IS_A, PREC> : LoadRowK<ROWS, VEC, NT, IS_A, PREC> {};
+struct Loader<A_ROWK, ROWS, VEC, NT, IS_A, PREC> : LoadRowK<ROWS, VEC, NT, IS_A, PREC> {};
 template <int ROWS, int VEC, int NT, bool IS_A, int PREC>
-struct Loader<1, ROWS, VEC, NT, IS_A, PREC> : LoadColK<ROWS, VEC, NT, IS_A, PREC> {};
+struct Loader<A_COLM, ROWS, VEC, NT, IS_A, PREC> : LoadColK<ROWS, VEC, NT, IS_A, PREC> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<2, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_FWD, PREC> {};
+struct Loader<A_CONV_FWD, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_FWD, PREC> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<3, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_UPS, PREC> {};
+struct Loader<A_CONV_UPS, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_UPS, PREC> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<4, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_DGRAD, PREC> {};
+struct Loader<A_CONV_DGRAD, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_DGRAD, PREC> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<2, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_FWD, PREC> {};
+struct Loader<A_CONV_SUBPIX, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_SUBPIX, PREC> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<3, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_UPS, PREC> {};
+struct Loader<A_COLM_PIX, ROWS, VEC, NT, true, PREC> : LoadColPix<ROWS, VEC, NT, PREC> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<5, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_SUBPIX, PREC> {};
+struct Loader<A_CONV_FWD_SPLIT, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_FWD, PREC, true> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<6, ROWS, VEC, NT, true, PREC> : LoadColPix<ROWS, VEC, NT, PREC> {};
+struct Loader<A_CONV_DGRAD_SPLIT, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_DGRAD, PREC, true> {};
 template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<4, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_SUBPIX, PREC> {};
-template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<5, ROWS, VEC, NT, false, PREC> : LoadRowK<ROWS, VEC, NT, false, PREC, true> {};
-template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<7, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_FWD, PREC, true> {};
-template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<6, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_FWD, PREC, true> {};
-template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<8, ROWS, VEC, NT, true, PREC> : LoadConvA<ROWS, VEC, NT, MODE_DGRAD, PREC, true> {};
-template <int ROWS, int VEC, int NT, int PREC>
-struct Loader<9, ROWS, VEC, NT, true, PREC> : LoadColK<ROWS, VEC, NT, true, PREC, true> {};
+struct Loader<A_COLM_SPLIT, ROWS, VEC, NT, true, PREC> : LoadColK<ROWS, VEC, NT, true, PREC, true> {};
 template <int ROWS, int VEC, int NT, int PREC>
 struct Loader<A_ROWK_SPLIT, ROWS, VEC, NT, true, PREC> : LoadRowK<ROWS, VEC, NT, true, PREC, true> {};
+template <int ROWS, int VEC, int NT, int PREC>
+struct Loader<B_WGRAD_FWD, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_FWD, PREC> {};
+template <int ROWS, int VEC, int NT, int PREC>
+struct Loader<B_WGRAD_UPS, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_UPS, PREC> {};
+template <int ROWS, int VEC, int NT, int PREC>
+struct Loader<B_WGRAD_SUBPIX, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_SUBPIX, PREC> {};
+template <int ROWS, int VEC, int NT, int PREC>
+struct Loader<B_ROWK_SPLIT, ROWS, VEC, NT, false, PREC> : LoadRowK<ROWS, VEC, NT, false, PREC, true> {};
+template <int ROWS, int VEC, int NT, int PREC>
+struct Loader<B_WGRAD_FWD_SPLIT, ROWS, VEC, NT, false, PREC> : LoadWgradX<ROWS, VEC, NT, MODE_FWD, PREC, true> {};
 template <int ROWS, int VEC, int NT, int PREC>
 struct Loader<B_COLN_SPLIT, ROWS, VEC, NT, false, PREC> : LoadColK<ROWS, VEC, NT, false, PREC, true> {};
 template <int ROWS, int VEC, int NT, int PREC>
@@ -1277,14 +1246,41 @@ struct Loader<B_WGRAD_P2, ROWS, VEC, NT, false, PREC> : LoadWgradXP2<ROWS, NT, P
 template <int ROWS, int VEC, int NT, int PREC>
 struct Loader<B_WGRAD_P2_SPLIT, ROWS, VEC, NT, false, PREC> : LoadWgradXP2<ROWS, NT, PREC, true> {};
 
+// XCD-aware remap of workgroup lin of a grid of n (bijective): blocks b and b+8 share an XCD, so hand each XCD a
+// contiguous run of tiles (row-major over (m, n): neighbours share A rows and the same weight panel).
+__device__ __forceinline__ int xcd_remap(int lin, int n) {
+  int out = lin;
+  if (n >= 16) {
+    const int xcd = lin & 7, q = n >> 3, r = n & 7;
+    out = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+  }
+  return out;
+}
+// tile of one batch entry / split -> (tm, tn): row-major, or the grouped order (GemmArgs::xcd_groups); both bijective
+// on [0, tiles_m * tiles_n)
+__device__ __forceinline__ void tile_order(const GemmArgs& a, int tile, int& tm, int& tn) {
+  if (a.xcd_groups > 1 && a.tiles_n > 1) {
+    const int gw = (a.tiles_n + a.xcd_groups - 1) / a.xcd_groups;
+    const int ng = (a.tiles_n + gw - 1) / gw;
+    const int g = min(tile / (a.tiles_m * gw), ng - 1);
+    const int rem = tile - g * a.tiles_m * gw;
+    const int width = g == ng - 1 ? a.tiles_n - g * gw : gw;
+    tm = rem / width;
+    tn = g * gw + (rem - tm * width);
+  } else {
+    tm = tile / a.tiles_n;
+    tn = tile - tm * a.tiles_n;
+  }
+}
+
 template <int BM, int BN, int WGM, int WGN, int AK, int VA, int BKIND, int VB, int PREC>
 __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
   constexpr int NT = 64 * WGM * WGN;
-#ifndef MVAE_COL_MF16  // COL-image (weight-gradient) register-staged loops on 16x16x32 MFMAs (-DMVAE_COL_MF16=0: 32x32x16)
-#define MVAE_COL_MF16 1
-#endif
-  constexpr int MF = (MVAE_COL_MF16 && PREC < 4 && mf_of(AK) == 32) ? 16 : mf_of(AK);
-  constexpr int KS = ks_of<MF>(), NR = nr_of<MF>();
+  // Register-staged loops (PREC 0/1/3) always run on 16x16x32 MFMAs, COL-image (weight-gradient) operands included
+  // (c4 step -1.1 % against 32x32x16, profiles/r05_col_mf16_ab.txt); of the LDS-DMA loops (PREC 4/5) ROW x ROW runs on
+  // 16x16x32 and COL x COL on 32x32x16.
+  constexpr int MF = (PREC >= 4 && AK == A_COLM) ? 32 : 16;
+  constexpr int NR = nr_of<MF>();
   using acc_t = acc_of<MF>;
   constexpr int LP = PREC == 4 ? 1 : PREC == 5 ? 3 : PREC;  // arithmetic of the register-staged loaders
   using LA = Loader<AK, BM, VA, NT, true, LP>;
@@ -1298,33 +1294,14 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WGN, wn = wid - wm * WGN;
-  // XCD-aware remap (bijective): blocks b and b+8 share an XCD, so hand each XCD a contiguous run
-  // of tiles (row-major over (m, n): neighbours share A rows and the same weight panel).
-  // The remap runs over the whole grid (tiles x batch x splits, split-major) since workgroups are
+  // The XCD remap runs over the whole grid (tiles x batch x splits, split-major) since workgroups are
   // dealt to XCDs round-robin by their linear id: the blocks of one split (same K range) share an L2.
   const int ntile = a.tiles_m * a.tiles_n;
   const int nwg = ntile * gridDim.z;
-  const int orig = blockIdx.x + ntile * blockIdx.z;
-  int lin = orig;
-  if (nwg >= 16) {
-    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  const int lin = xcd_remap(blockIdx.x + ntile * blockIdx.z, nwg);
   const int z = lin / ntile;
-  const int tile = lin - z * ntile;
   int tm, tn;
-  if (a.xcd_groups > 1 && a.tiles_n > 1) {  // grouped order (GemmArgs::xcd_groups), bijective on [0, ntile)
-    const int gw = (a.tiles_n + a.xcd_groups - 1) / a.xcd_groups;
-    const int ng = (a.tiles_n + gw - 1) / gw;
-    const int g = min(tile / (a.tiles_m * gw), ng - 1);
-    const int rem = tile - g * a.tiles_m * gw;
-    const int width = g == ng - 1 ? a.tiles_n - g * gw : gw;
-    tm = rem / width;
-    tn = g * gw + (rem - tm * width);
-  } else {
-    tm = tile / a.tiles_n;
-    tn = tile - tm * a.tiles_n;
-  }
+  tile_order(a, lin - z * ntile, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   const int bidx = z / a.splits, split = z - bidx * a.splits;
   const int kb = split * a.k_split;
@@ -1356,8 +1333,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
     constexpr bool ACOL = AK == A_COLM,
                    BCOL = BKIND == B_WGRAD_FWD || BKIND == B_WGRAD_SUBPIX || BKIND == B_WGRAD_P2 || BKIND == B_COLN;
     static_assert(ACOL == BCOL && MF == (ACOL ? 32 : 16), "DMA main loop: ROW x ROW (MF 16) or COL x COL (MF 32)");
-    using DA = DmaLoader<AK == A_ROWK ? 0 : AK, BM, NT, true, KT>;
-    using DB = DmaLoader<BKIND == B_ROWK ? 0 : BKIND, BN, NT, false, KT>;
+    using DA = DmaLoader<AK, BM, NT, true, KT>;
+    using DB = DmaLoader<BKIND, BN, NT, false, KT>;
     constexpr int PA = BM * KT, PB = BN * KT;  // plane sizes (elements)
     constexpr int SBUF = NPL * (PA + PB);      // one stage
     static_assert(2 * SBUF * 2 <= 163840, "DMA stages exceed the LDS");
@@ -1390,8 +1367,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
     };
     constexpr int DKS = KT / (MF == 32 ? 16 : 32);   // MFMA k-steps per stage
     constexpr int RPF = ACOL ? 2 : 1;                // LDS read instructions per fragment
-    // (measured, c5 shapes: the spread issue gains 3-6 % on the weight-gradient loops and loses 0-3 % on fwd / dgrad)
-    constexpr bool SPREAD = MVAE_DMA_SPREAD == 2 || (MVAE_DMA_SPREAD == 1 && ACOL);
+    // SPREAD: the COL (weight-gradient) loops spread their DMA issue over the k-steps (measured, c5 shapes: the spread
+    // issue gains 3-6 % on the weight-gradient loops and loses 0-3 % on fwd / dgrad)
+    constexpr bool SPREAD = ACOL;
     if (nt > 0) issue(lds);
     for (int t = 0; t < nt; ++t) {
       __bf16* cur = lds + (t & 1) * SBUF;
@@ -1481,7 +1459,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
   LA la;
   LB lb;
   // wgrad: only the first column of tiles publishes the bias gradient (row sums of dY^T): the others skip the sums
-  if constexpr (AK == A_COLM || AK == A_COLM_PIX || AK == A_COLM_SPLIT) la.want_bs = a.bias_ws != nullptr && tn == 0;
+  if constexpr (a_is_col(AK)) la.want_bs = a.bias_ws != nullptr && tn == 0;
   la.init(a, a.A + bidx * a.sA, m0, kb, tid, bidx);
   lb.init(a, a.B + bidx * a.sB, n0, kb, tid, bidx);
 
@@ -1509,43 +1487,38 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
   // free buffer, immediately re-issues the global loads of tile t+2 into the same registers, and
   // multiplies tile t -- whose buffer was completed before the barrier -- so the LDS writes and the
   // VALU split overlap the wave's own MFMAs and the global loads have a whole phase to land.
-  auto compute = [&](const __bf16* Ai) {
+  auto compute = [&](const __bf16* Ai) {  // one K-tile: one 16x16x32 k-step
     const __bf16* Bi = Ai + IA::SIZE;
+    bf16x8 bh[TN], bl[TN];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      bf16x8 bh[TN], bl[TN];
+    for (int j = 0; j < TN; ++j) {
+      bh[j] = read_frag<BN, LB::COL>(Bi, brow + j * MF, lane);
+      if constexpr (PREC != 1) bl[j] = read_frag<BN, LB::COL>(Bi + IB::PLANE, brow + j * MF, lane);
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const bf16x8 ah = read_frag<BM, LA::COL>(Ai, arow + i * MF, lane);
+      bf16x8 al{};
+      if constexpr (PREC != 1) al = read_frag<BM, LA::COL>(Ai + IA::PLANE, arow + i * MF, lane);
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, ks, lane);
-        if constexpr (PREC != 1) bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, ks, lane);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const bf16x8 ah = read_frag<BM, LA::COL, MF>(Ai, arow + i * MF, ks, lane);
-        bf16x8 al{};
-        if constexpr (PREC != 1) al = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow + i * MF, ks, lane);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          mma<PREC>(acc[i][j], ah, al, bh[j], bl[j]);
-        }
+        mma<PREC>(acc[i][j], ah, al, bh[j], bl[j]);
       }
     }
   };
   int t = 0;
-  {
-#ifndef MVAE_BLOCK_STAGING
-  // steady state, software-pipelined by hand: the K-tile's KS*TM MFMA steps (one MF-row A fragment
+  // steady state, software-pipelined by hand: the K-tile's TM MFMA steps (one MF-row A fragment
   // x TN B fragments x 3 split products each) each carry a share of the staging work -- split +
   // LDS write of one slot of tile t+1, then the global load of the same slot of tile t+2 -- and
   // prefetch the next step's A fragment. sched_barrier pins that order (the scheduler would
   // otherwise hoist all staging VALU into one block ahead of the MFMAs, idling the MFMA pipe).
-  constexpr int STEPS = KS * TM;
   constexpr int NSL = LA::NS + LB::NS;
-  // STAG: the wave runs each step's staging share BEFORE its MFMAs instead of after. Given to the
-  // second half of the workgroup (waves 4-7 share SIMDs with waves 0-3), it staggers the two waves of
-  // every SIMD: one issues VALU/LDS staging while its partner's MFMAs occupy the matrix pipe.
-  auto kloop = [&](auto stag) {
-    constexpr bool STAG = decltype(stag)::value;
+  // the second-dispatched half of the workgroup loses every VALU arbitration to its SIMD partner: one static
+  // priority raise for it (no per-segment flips): wgrad +1-3 %, fwd / dgrad within noise (tools/ab.sh)
+  if (NT >= 512 && wid >= (NT / 64) / 2) __builtin_amdgcn_s_setprio(1);
+  // (The loop stays in a lambda, called once: written straight into the kernel body the same source compiles to
+  // differently scheduled staging in every register-staged kernel -- profiles/gemm_refactor_pieces.txt, "plain loop".)
+  auto kloop = [&] {
     for (; t + 2 < nt; ++t) {
       __bf16* nb = lds + ((t & 1) ^ 1) * BUF;
       const __bf16* Ai = lds + (t & 1) * BUF;
@@ -1557,14 +1530,14 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
       bf16x8 bh[TN], bl[TN], ah[2], al[2];
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, 0, lane);
-        if constexpr (PREC != 1) bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, 0, lane);
+        bh[j] = read_frag<BN, LB::COL>(Bi, brow + j * MF, lane);
+        if constexpr (PREC != 1) bl[j] = read_frag<BN, LB::COL>(Bi + IB::PLANE, brow + j * MF, lane);
       }
-      ah[0] = read_frag<BM, LA::COL, MF>(Ai, arow, 0, lane);
-      if constexpr (PREC != 1) al[0] = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow, 0, lane);
+      ah[0] = read_frag<BM, LA::COL>(Ai, arow, lane);
+      if constexpr (PREC != 1) al[0] = read_frag<BM, LA::COL>(Ai + IA::PLANE, arow, lane);
       auto stage = [&](int st) {
 #pragma unroll
-        for (int q = st * NSL / STEPS; q < (st + 1) * NSL / STEPS; ++q) {
+        for (int q = st * NSL / TM; q < (st + 1) * NSL / TM; ++q) {
           if (q < LA::NS) {
             la.store_slot(nb, q);
             la.load_slot(a, q);
@@ -1575,64 +1548,24 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
         }
       };
 #pragma unroll
-      for (int st = 0; st < STEPS; ++st) {
-        const int i = st % TM, cur = st & 1;
-        if constexpr (STAG) {
-          stage(st);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (st + 1 < STEPS) {
-          const int ks1 = (st + 1) / TM, i1 = (st + 1) % TM;
-          ah[cur ^ 1] = read_frag<BM, LA::COL, MF>(Ai, arow + i1 * MF, ks1, lane);
-          if constexpr (PREC != 1) al[cur ^ 1] = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow + i1 * MF, ks1, lane);
+      for (int i = 0; i < TM; ++i) {
+        const int cur = i & 1;
+        if (i + 1 < TM) {
+          ah[cur ^ 1] = read_frag<BM, LA::COL>(Ai, arow + (i + 1) * MF, lane);
+          if constexpr (PREC != 1) al[cur ^ 1] = read_frag<BM, LA::COL>(Ai + IA::PLANE, arow + (i + 1) * MF, lane);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           mma<PREC>(acc[i][j], ah[cur], al[cur], bh[j], bl[j]);
         }
-        if (KS == 2 && st == TM - 1) {  // B fragments of the second k-half
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, 1, lane);
-            if constexpr (PREC != 1) bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, 1, lane);
-          }
-        }
-        if constexpr (!STAG) stage(st);
+        stage(i);
         __builtin_amdgcn_sched_barrier(0);
       }
       __syncthreads();
     }
   };
-#ifndef MVAE_NO_PRIO
-  // the second-dispatched half of the workgroup loses every VALU arbitration to its SIMD partner: one static
-  // priority raise for it (no per-segment flips): wgrad +1-3 %, fwd / dgrad within noise (tools/ab.sh)
-  if (NT >= 512 && wid >= (NT / 64) / 2) __builtin_amdgcn_s_setprio(1);
-#endif
-#ifdef MVAE_STAG
-  if (NT >= 512 && wid >= (NT / 64) / 2)
-    kloop(std::true_type{});
-  else
-    kloop(std::false_type{});
-#else
-    kloop(std::false_type{});
-#endif
-#ifndef MVAE_NO_PRIO
+  kloop();
   __builtin_amdgcn_s_setprio(0);
-#endif
-#else
-  for (; t + 2 < nt; ++t) {  // block staging: all of tile t+1's staging, then tile t's MFMAs
-    __bf16* nb = lds + ((t & 1) ^ 1) * BUF;
-    la.store(nb);
-    lb.store(nb + IA::SIZE);
-    la.advance();
-    lb.advance();
-    la.load(a);
-    lb.load(a);
-    compute(lds + (t & 1) * BUF);
-    __syncthreads();
-  }
-#endif
-  }
   if (t + 1 < nt) {  // last staged tile: write it, nothing left to load
     __bf16* nb = lds + ((t & 1) ^ 1) * BUF;
     la.store(nb);
@@ -1646,7 +1579,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
 
   // wgrad: the conv bias gradient (row sums of A = dY^T over this split's pixels) falls out of the
   // A staging for free; one column of tiles (tn == 0) publishes it, fixed-order reduction in LDS.
-  if constexpr (AK == A_COLM || AK == A_COLM_PIX || AK == A_COLM_SPLIT) {
+  if constexpr (a_is_col(AK)) {
     if (a.bias_ws != nullptr && tn == 0) {
       constexpr int KRN = NT / (BM / 4);
       float* red = (float*)lds;
@@ -1869,9 +1802,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_kernel(GemmArgs a) {
 template <int BM, int BN, int WGM, int WGN, int AK, int VA, int BKIND, int VB, int PREC>
 __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs a) {
   constexpr int NT = 64 * WGM * WGN;
-  constexpr int MF = (MVAE_COL_MF16 && mf_of(AK) == 32) ? 16 : mf_of(AK);
-  static_assert(MF == 16 && (PREC == 0 || PREC == 3), "persistent GEMM: 16x16x32 tiles, 3xBF16 or exact fp32");
-  constexpr int KS = ks_of<MF>(), NR = nr_of<MF>();
+  constexpr int MF = 16;  // register-staged: 16x16x32 MFMAs
+  static_assert(PREC == 0 || PREC == 3, "persistent GEMM: 3xBF16 or exact fp32");
+  constexpr int NR = nr_of<MF>();
   using acc_t = acc_of<MF>;
   using LA = Loader<AK, BM, VA, NT, true, PREC>;
   using LB = Loader<BKIND, BN, VB, NT, false, PREC>;
@@ -1886,28 +1819,13 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs
   const int wm = wid / WGN, wn = wid - wm * WGN;
   const int arow = wm * (BM / WGM), brow = wn * (BN / WGN);
   const int ntile = a.tiles_m * a.tiles_n, total = ntile * a.batch, grid = (int)gridDim.x;
-  int lin = blockIdx.x;
-  if (grid >= 16) {  // XCD-aware remap over the grid (bijective, as gemm3x_kernel's)
-    const int xcd = lin & 7, q = grid >> 3, r = grid & 7;
-    lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
-  }
-  // tile l of the sequence -> (m0, n0, batch entry); gemm3x_kernel's orders
+  const int lin = xcd_remap(blockIdx.x, grid);
+  // tile l of the sequence -> (m0, n0, batch entry)
   auto locate = [&](int l, int& m0, int& n0, int& bidx) {
     bidx = l / ntile;
     const int tile = l - bidx * ntile;
     int tm, tn;
-    if (a.xcd_groups > 1 && a.tiles_n > 1) {
-      const int gw = (a.tiles_n + a.xcd_groups - 1) / a.xcd_groups;
-      const int ng = (a.tiles_n + gw - 1) / gw;
-      const int g = min(tile / (a.tiles_m * gw), ng - 1);
-      const int rem = tile - g * a.tiles_m * gw;
-      const int width = g == ng - 1 ? a.tiles_n - g * gw : gw;
-      tm = rem / width;
-      tn = g * gw + (rem - tm * width);
-    } else {
-      tm = tile / a.tiles_n;
-      tn = tile - tm * a.tiles_n;
-    }
+    tile_order(a, tile, tm, tn);
     m0 = tm * BM;
     n0 = tn * BN;
   };
@@ -1925,23 +1843,20 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs
     lb.load(a);
   };
   acc_t acc[TM][TN];
-  auto compute = [&](const __bf16* Ai) {
+  auto compute = [&](const __bf16* Ai) {  // one K-tile: one 16x16x32 k-step
     const __bf16* Bi = Ai + IA::SIZE;
+    bf16x8 bh[TN], bl[TN];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      bf16x8 bh[TN], bl[TN];
+    for (int j = 0; j < TN; ++j) {
+      bh[j] = read_frag<BN, LB::COL>(Bi, brow + j * MF, lane);
+      bl[j] = read_frag<BN, LB::COL>(Bi + IB::PLANE, brow + j * MF, lane);
+    }
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, ks, lane);
-        bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, ks, lane);
-      }
+    for (int i = 0; i < TM; ++i) {
+      const bf16x8 ah = read_frag<BM, LA::COL>(Ai, arow + i * MF, lane);
+      const bf16x8 al = read_frag<BM, LA::COL>(Ai + IA::PLANE, arow + i * MF, lane);
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const bf16x8 ah = read_frag<BM, LA::COL, MF>(Ai, arow + i * MF, ks, lane);
-        const bf16x8 al = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow + i * MF, ks, lane);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma<PREC>(acc[i][j], ah, al, bh[j], bl[j]);
-      }
+      for (int j = 0; j < TN; ++j) mma<PREC>(acc[i][j], ah, al, bh[j], bl[j]);
     }
   };
 
@@ -1969,12 +1884,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs
     __syncthreads();
     int t = 0;
     // steady state: gemm3x_kernel's hand-pipelined K loop (staging of tile t+1 / loads of tile t+2 spread over the
-    // MFMA steps of tile t)
-    constexpr int STEPS = KS * TM;
+    // MFMA steps of tile t). A COPY, together with compute above and the tail below: as one forceinline function
+    // called by both kernels the loop compiles to different code in every register-staged kernel (same MFMA / barrier
+    // sequence and no more registers, but unmeasured: profiles/gemm_refactor_pieces.txt, "K loop"). Change both.
     constexpr int NSL = LA::NS + LB::NS;
-#ifndef MVAE_NO_PRIO
     if (NT >= 512 && wid >= (NT / 64) / 2) __builtin_amdgcn_s_setprio(1);
-#endif
     for (; t + 2 < nt; ++t) {
       __bf16* nb = lds + ((t & 1) ^ 1) * BUF;
       const __bf16* Ai = lds + (t & 1) * BUF;
@@ -1986,14 +1900,14 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs
       bf16x8 bh[TN], bl[TN], ah[2], al[2];
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, 0, lane);
-        bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, 0, lane);
+        bh[j] = read_frag<BN, LB::COL>(Bi, brow + j * MF, lane);
+        bl[j] = read_frag<BN, LB::COL>(Bi + IB::PLANE, brow + j * MF, lane);
       }
-      ah[0] = read_frag<BM, LA::COL, MF>(Ai, arow, 0, lane);
-      al[0] = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow, 0, lane);
+      ah[0] = read_frag<BM, LA::COL>(Ai, arow, lane);
+      al[0] = read_frag<BM, LA::COL>(Ai + IA::PLANE, arow, lane);
       auto stage = [&](int st) {
 #pragma unroll
-        for (int q = st * NSL / STEPS; q < (st + 1) * NSL / STEPS; ++q) {
+        for (int q = st * NSL / TM; q < (st + 1) * NSL / TM; ++q) {
           if (q < LA::NS) {
             la.store_slot(nb, q);
             la.load_slot(a, q);
@@ -2004,30 +1918,20 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs
         }
       };
 #pragma unroll
-      for (int st = 0; st < STEPS; ++st) {
-        const int i = st % TM, cur = st & 1;
-        if (st + 1 < STEPS) {
-          const int ks1 = (st + 1) / TM, i1 = (st + 1) % TM;
-          ah[cur ^ 1] = read_frag<BM, LA::COL, MF>(Ai, arow + i1 * MF, ks1, lane);
-          al[cur ^ 1] = read_frag<BM, LA::COL, MF>(Ai + IA::PLANE, arow + i1 * MF, ks1, lane);
+      for (int i = 0; i < TM; ++i) {
+        const int cur = i & 1;
+        if (i + 1 < TM) {
+          ah[cur ^ 1] = read_frag<BM, LA::COL>(Ai, arow + (i + 1) * MF, lane);
+          al[cur ^ 1] = read_frag<BM, LA::COL>(Ai + IA::PLANE, arow + (i + 1) * MF, lane);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) mma<PREC>(acc[i][j], ah[cur], al[cur], bh[j], bl[j]);
-        if (KS == 2 && st == TM - 1) {  // B fragments of the second k-half
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            bh[j] = read_frag<BN, LB::COL, MF>(Bi, brow + j * MF, 1, lane);
-            bl[j] = read_frag<BN, LB::COL, MF>(Bi + IB::PLANE, brow + j * MF, 1, lane);
-          }
-        }
-        stage(st);
+        stage(i);
         __builtin_amdgcn_sched_barrier(0);
       }
       __syncthreads();
     }
-#ifndef MVAE_NO_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     if (t + 1 < nt) {  // last staged K-tile: write it, nothing left to load
       __bf16* nb = lds + ((t & 1) ^ 1) * BUF;
       la.store(nb);
@@ -2039,6 +1943,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm3x_persist_kernel(GemmArgs
     compute(lds + (t & 1) * BUF);
     if (more) prefetch(lnext);  // in flight under the epilogue
 
+    // A COPY of the staging half of gemm3x_kernel's 16-B epilogue: as one forceinline function with a compile-time
+    // PLAIN form it costs gemm3x_kernel registers (128x128 3xBF16 conv: 212 -> 216 VGPRs;
+    // profiles/gemm_refactor_pieces.txt, "16-B epilogue"). Change both.
     // 16-B epilogue through LDS (gemm3x_kernel's vec_epi form): each wave stages half of its accumulator block at a
     // time as fp32 rows and stores float4 runs of the row; rows / columns outside the matrix are dropped by the
     // descriptor. The stores stay in flight into the next tile.
@@ -2143,26 +2050,27 @@ enum { T256x256 = 0, T256x128 = 1, T128x256 = 2, T128x128 = 3, T64x64 = 4, T128x
 enum { MATH_3XBF16 = 0, MATH_BF16 = 1, MATH_FP32 = 2 };
 int math_mode();
 
-// workgroups of a tile config resident per CU at once (LDS-bound: 160, 120, 120, 80, 40 KB per workgroup; the skinny
-// tile 4): a "round" of a launch is 256 CUs x this many tiles
-inline int resident_of(int cfg) {
-  static const int r[6] = {1, 1, 1, 2, 4, 4};
-  return (cfg >= 0 && cfg < 6) ? r[cfg] : 1;
+// The tile configurations: edge lengths (rows of M, columns of N), waves along each, and the workgroups resident per
+// CU at once (LDS-bound: 160, 120, 120, 80, 40 KB per workgroup; the skinny tile 4) -- a "round" of a launch is
+// 256 CUs x this many tiles
+struct TileCfg {
+  int bm, bn, wgm, wgn, resident;
+};
+constexpr int NUM_TILE_CFGS = 6;
+constexpr TileCfg TILE_CFGS[NUM_TILE_CFGS] = {{256, 256, 2, 4, 1}, {256, 128, 4, 2, 1}, {128, 256, 2, 4, 1},
+                                              {128, 128, 2, 2, 2}, {64, 64, 2, 2, 4},   {128, 16, 2, 1, 4}};
+// every host-side reader goes through tile_cfg: a config outside the table reads as a 64x64 tile, one per CU
+inline const TileCfg& tile_cfg(int cfg) {
+  static constexpr TileCfg unknown = {64, 64, 2, 2, 1};
+  return (cfg >= 0 && cfg < NUM_TILE_CFGS) ? TILE_CFGS[cfg] : unknown;
 }
-// tile edge lengths of a config (rows of M, columns of N)
-inline int tile_m_of(int cfg) {
-  static const int m[6] = {256, 256, 128, 128, 64, 128};
-  return (cfg >= 0 && cfg < 6) ? m[cfg] : 64;
-}
-inline int tile_n_of(int cfg) {
-  static const int n[6] = {256, 128, 256, 128, 64, 16};
-  return (cfg >= 0 && cfg < 6) ? n[cfg] : 64;
-}
+inline int resident_of(int cfg) { return tile_cfg(cfg).resident; }
+inline int tile_m_of(int cfg) { return tile_cfg(cfg).bm; }
+inline int tile_n_of(int cfg) { return tile_cfg(cfg).bn; }
+inline int tile_area_of(int cfg) { return tile_cfg(cfg).bm * tile_cfg(cfg).bn; }
 
 inline long long tiles_of(int cfg, const GemmArgs& a) {
-  static const int TM_[] = {256, 256, 128, 128, 64, 128};
-  static const int TN_[] = {256, 128, 256, 128, 64, 16};
-  return (long long)cdiv(a.M, TM_[cfg]) * cdiv(a.N, TN_[cfg]) * a.batch;
+  return (long long)cdiv(a.M, tile_cfg(cfg).bm) * cdiv(a.N, tile_cfg(cfg).bn) * a.batch;
 }
 
 // largest useful split-K factor (>= 16 K-tiles per split)
@@ -2195,18 +2103,17 @@ inline int choose_tile(const GemmArgs& a, bool allow_big, bool can_split) {
     // time ~ rounds x (tiles resident per CU) x tile area / per-tile efficiency, with rounds =
     // ceil(tiles / (256 CUs x tiles resident per CU)). Efficiencies are the measured full-chip rates of each
     // tile relative to 256x256 (tools/tile_sweep.py, c4 shapes: 256x256 1.0, 256x128 / 128x256 0.82,
-    // 128x128 0.70, 64x64 0.50); residency from LDS (160, 120, 120, 80, 40 KB per workgroup). The rule it
+    // 128x128 0.70, 64x64 0.50); residency and area from TILE_CFGS. The rule it
     // replaces (largest tile with >= 240 tiles) lost 18-65 % on the c2 / c3 layers (7x7 and 14x14 at 256-512
     // channels; 32-64 channels at 14x14-28x28).
     static const double eff[5] = {1.0, 0.82, 0.82, 0.70, 0.50};
-    static const int res[5] = {1, 1, 1, 2, 4};
-    static const int area[5] = {65536, 32768, 32768, 16384, 4096};
     int best = T64x64;
     double best_t = 1e300;
     for (int c = T256x256; c <= T64x64; ++c) {
       const long long t = tiles_of(c, a);
-      const double rounds = (double)((t + 256LL * res[c] - 1) / (256LL * res[c]));
-      const double cost = rounds * res[c] * area[c] / eff[c];
+      const int res = resident_of(c);
+      const double rounds = (double)((t + 256LL * res - 1) / (256LL * res));
+      const double cost = rounds * res * tile_area_of(c) / eff[c];
       if (cost < best_t * 0.999) { best_t = cost; best = c; }
     }
     return best;
@@ -2238,15 +2145,7 @@ inline bool vec_epi_disabled() {
 // PO >= 0 forces the kernel arithmetic (PREC 4: bf16-stored operands through the LDS-DMA main loop)
 template <int CFG, int AK, int VA, int BKIND, int VB, int PO = -1>
 void launch_cfg(GemmArgs& a, hipStream_t st) {
-  constexpr int BM = CFG == T256x256 || CFG == T256x128 ? 256 : CFG == T64x64 ? 64 : 128;
-  constexpr int BN = CFG == T256x256 || CFG == T128x256 ? 256 : CFG == T64x64 ? 64 : CFG == T128x16 ? 16
-                   : 128;
-  constexpr int WGM = CFG == T256x128 ? 4 : 2;
-#ifdef MVAE_W4
-  constexpr int WGN = CFG == T128x256 ? 4 : CFG == T128x16 ? 1 : 2;  // 256x256 on 4 waves
-#else
-  constexpr int WGN = (CFG == T256x256 || CFG == T128x256) ? 4 : CFG == T128x16 ? 1 : 2;
-#endif
+  constexpr int BM = TILE_CFGS[CFG].bm, BN = TILE_CFGS[CFG].bn, WGM = TILE_CFGS[CFG].wgm, WGN = TILE_CFGS[CFG].wgn;
   a.tiles_m = cdiv(a.M, BM);
   a.tiles_n = cdiv(a.N, BN);
   if (a.xcd_groups <= 0) a.xcd_groups = xcd_groups_env();
@@ -2279,8 +2178,8 @@ void launch_big(GemmArgs& a, hipStream_t st, int cfg) {
     case T256x128: launch_cfg<T256x128, AK, VA, BKIND, VB>(a, st); break;
     case T128x256: launch_cfg<T128x256, AK, VA, BKIND, VB>(a, st); break;
     case T128x128: launch_cfg<T128x128, AK, VA, BKIND, VB>(a, st); break;
-    case T128x16:  // 16-wide tiles need the 16x16x32 MFMA shape
-      if constexpr (mf_of(AK) == 16) launch_cfg<T128x16, AK, VA, BKIND, VB>(a, st);
+    case T128x16:  // (the skinny tile is built for ROW-image A operands only)
+      if constexpr (!a_is_col(AK)) launch_cfg<T128x16, AK, VA, BKIND, VB>(a, st);
       else launch_cfg<T64x64, AK, VA, BKIND, VB>(a, st);
       break;
     default: launch_cfg<T64x64, AK, VA, BKIND, VB>(a, st); break;
@@ -2330,8 +2229,7 @@ inline void set_splits(GemmArgs& a, int splits) {
 // K = 25k-400k pixels) with one workgroup per CU runs its K loop latency-bound (one tile in flight per CU).
 constexpr int MAX_SPLITS = 256;
 inline int choose_splits(const GemmArgs& a, int cfg) {
-  static const int res_of[6] = {1, 1, 1, 2, 4, 4};
-  const long long slots = 256LL * res_of[cfg];
+  const long long slots = 256LL * resident_of(cfg);
   const long long tiles = tiles_of(cfg, a);
   const int ms = std::max(1, (int)std::min<long long>(MAX_SPLITS, a.K / 256));
   if (tiles >= 4 * slots) return 1;
@@ -2357,14 +2255,12 @@ inline int choose_splits(const GemmArgs& a, int cfg) {
 // K-tiles each and must fit ws_bytes.
 inline int conv_split_cfg(const GemmArgs& a, int cfg0, size_t ws_bytes, int* splits_out) {
   static const double eff[5] = {1.0, 0.82, 0.82, 0.70, 0.50};
-  static const int res[5] = {1, 1, 1, 2, 4};
-  static const int area[5] = {65536, 32768, 32768, 16384, 4096};
   if (cfg0 < T256x256 || cfg0 > T64x64 || ws_bytes == 0 || a.batch != 1) return -1;
   const double mac_rate = 0.9e12;  // MAC/s per CU at 256x256 (efficiency 1.0): ~470 TF/s chip-wide, 3xBF16
   auto gemm_s = [&](int c, long long blocks, double k) {
-    const long long slots = 256LL * res[c];
+    const long long slots = 256LL * resident_of(c);
     const double rounds = (double)((blocks + slots - 1) / slots);
-    return rounds * res[c] * area[c] * k / eff[c] / mac_rate;
+    return rounds * resident_of(c) * tile_area_of(c) * k / eff[c] / mac_rate;
   };
   const double t0 = gemm_s(cfg0, tiles_of(cfg0, a), (double)a.K);
   const double mn4 = 4.0 * (double)a.M * (double)a.N;

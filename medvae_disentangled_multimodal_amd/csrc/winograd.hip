@@ -930,8 +930,7 @@ static int wino_out_launch(WinoOut& p, int tile, bool gnb, void* stream) {
 // gemm3x_kernel). MVAE_NO_PERSISTENT_GEMM (read per call) keeps every launch on gemm3x_kernel: the A/B escape.
 template <int CFG, int AK, int BKIND>
 static bool persist_cfg(GemmArgs& a, hipStream_t st) {
-  constexpr int BM = 256, BN = CFG == T256x256 ? 256 : 128;
-  constexpr int WGM = CFG == T256x128 ? 4 : 2, WGN = CFG == T256x256 ? 4 : 2;
+  constexpr int BM = TILE_CFGS[CFG].bm, BN = TILE_CFGS[CFG].bn, WGM = TILE_CFGS[CFG].wgm, WGN = TILE_CFGS[CFG].wgn;
   a.tiles_m = cdiv(a.M, BM);
   a.tiles_n = cdiv(a.N, BN);
   const long long total = (long long)a.tiles_m * a.tiles_n * a.batch, slots = 256LL * resident_of(CFG);
@@ -952,9 +951,6 @@ static bool persist_cfg(GemmArgs& a, hipStream_t st) {
 template <int AK, int BKIND>
 static bool launch_persist(GemmArgs& a, hipStream_t st, int cfg) {
   static_assert(AK == A_ROWK_SPLIT && BKIND == B_ROWK_SPLIT, "persistent GEMM: pre-split ROW x ROW operands");
-#ifdef MVAE_W4  // (a build whose 256x256 tile runs on 4 waves)
-  return false;
-#else
   if (getenv("MVAE_NO_PERSISTENT_GEMM") != nullptr || math_mode() == MATH_BF16 || a.splits != 1 || a.bias || a.res ||
       a.beta != 0.f || a.out_remap || a.gn_part || a.gnb_part || a.bias_ws || (a.N & 3) || (a.ldc & 3) || (a.sC & 3) ||
       !al16(a.C) || vec_epi_disabled())
@@ -962,7 +958,6 @@ static bool launch_persist(GemmArgs& a, hipStream_t st, int cfg) {
   if (cfg == T256x256) return persist_cfg<T256x256, AK, BKIND>(a, st);
   if (cfg == T256x128) return persist_cfg<T256x128, AK, BKIND>(a, st);
   return false;
-#endif
 }
 
 }  // namespace mvae
