@@ -593,6 +593,21 @@ int mvae_latent_aux_bwd(const float* z, const long long* idx, int nb, int c, int
                         float* workspace, size_t ws_bytes, void* stream);
 size_t mvae_latent_aux_workspace_bytes(int nb, int d);
 
+/* ConditionalVAE FiLM conditioning (src/models/conditional_vae.py FiLMLayer.forward: features * scale[..., None, None]
+ * + shift[..., None, None]). x [nb][npix][c] with pixel stride ldx >= c (a channel slice of a wider NHWC tensor is read
+ * in place), scale / shift [nb][c] contiguous, y / dx [nb][npix][c] contiguous; fp32 throughout.
+ * fwd: y = x * scale + shift. bwd: dx = dy * scale (written only when write_dx != 0; dx and scale may be NULL
+ * otherwise), dscale[b][c] = sum_p dy * x, dshift[b][c] = sum_p dy, x and dy (pixel stride lddy) read once.
+ * 16-byte loads and stores when c, the strides and the pointers are multiples of 4 floats, 4-byte ones otherwise.
+ * The pixel sums are deterministic: a pixel split fixed by the shape, per-workgroup partials in the workspace
+ * (pscale [nb][nchunk][c] | pshift [nb][nchunk][c], fp32; size from the query), merged in index order. No atomics. */
+int mvae_film_fwd(const float* x, long long ldx, const float* scale, const float* shift, float* y, int nb, int npix,
+                  int c, void* stream);
+int mvae_film_bwd(const float* x, long long ldx, const float* dy, long long lddy, const float* scale, float* dx,
+                  float* dscale, float* dshift, int nb, int npix, int c, int write_dx, void* workspace,
+                  size_t workspace_bytes, void* stream);
+size_t mvae_film_workspace_bytes(int nb, int npix, int c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,9 @@ SIGNATURES = {
     "mvae_latent_aux_fwd": (I, [P, P, I, I, I, I, I, I, F, P, P, Z, P]),
     "mvae_latent_aux_bwd": (I, [P, P, I, I, I, I, I, I, F, P, P, P, P, P, Z, P]),
     "mvae_latent_aux_workspace_bytes": (Z, [I, I]),
+    "mvae_film_fwd": (I, [P, L, P, P, P, I, I, I, P]),
+    "mvae_film_bwd": (I, [P, L, P, L, P, P, P, P, I, I, I, I, P, Z, P]),
+    "mvae_film_workspace_bytes": (Z, [I, I, I]),
 }
 
 

@@ -245,7 +245,15 @@ class Encoder(nn.Module):
         self.norm_out = Normalize(block_in)
         self.conv_out = Conv2d(block_in, 2 * z_channels if double_z else z_channels, 3, 1, 1)
 
-    def forward(self, x):
+    def forward(self, x, film=None):
+        """film: None, or one (scale, shift) pair of [B, ch * ch_mult[i]] tensors per level -- the level's output is
+        modulated (ops.film) after its last block / attention, before its downsample (the last level's: before
+        mid.block_1). The modulated map is a plain tensor, so the Normalize that reads it next (through the downsample
+        conv, or mid.block_1's norm1 directly) computes its own statistics: the ones the level's last conv emitted
+        describe the map before the modulation."""
+        if film is not None and len(film) != self.num_resolutions:
+            raise ValueError(f"Encoder: film needs one (scale, shift) pair per level ({self.num_resolutions}), "
+                             f"got {len(film)}")
         h = self.conv_in(x, gn_stats=True)
         for i_level in range(self.num_resolutions):
             lvl = self.down[i_level]
@@ -253,6 +261,8 @@ class Encoder(nn.Module):
                 h = lvl.block[i_block](h)
                 if len(lvl.attn) > 0:
                     h = lvl.attn[i_block](h)
+            if film is not None:
+                h = ops.film(h, *film[i_level])
             if i_level != self.num_resolutions - 1:
                 h = lvl.downsample(h)
         h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(h)))

@@ -5,7 +5,8 @@ Activations are torch tensors with the reference's logical NCHW shapes stored ch
 gradients are written straight into the parameter's flat gradient slot (`p._mvae_main_grad`,
 attached by `FlatParameters`) and accumulated there (beta = 1), so autograd never materialises
 or adds them; without a flat slot the gradient is returned to autograd as usual.
-Every op requires CUDA(HIP) tensors: there is no CPU fallback.
+Every op requires CUDA(HIP) tensors: there is no CPU fallback (ops.film alone also takes CPU tensors, through plain
+torch, for the host-side tests of the conditioning).
 """
 from __future__ import annotations
 
@@ -2827,3 +2828,67 @@ class LatentAuxFn(torch.autograd.Function):
 
 def latent_aux_losses(z, idx, off: int, d: int, temperature: float = 0.1):
     return LatentAuxFn.apply(z, idx, off, d, temperature)
+
+
+# ------------------------------------------------------------------------------------------
+# FiLM conditioning (conditional_vae.py FiLMLayer.forward): y = x * scale[..., None, None] + shift[..., None, None],
+# one launch forward, two backward (csrc/film.hip); always fp32, whatever set_precision selects
+# ------------------------------------------------------------------------------------------
+class FilmFn(torch.autograd.Function):
+    """x [B, C, H, W] (channels_last, or a channel slice of a wider channels_last tensor, read in place), scale / shift
+    [B, C]. The backward reads x and dy once: dx = dy * scale (skipped when x needs no gradient), dscale / dshift =
+    the pixel sums of dy * x / dy, deterministic (fixed pixel split, partials in the arena workspace "film", merged in
+    index order). Launches are accounted under the GroupNorm family's tags (gn_fwd / gn_bwd: the same HBM-bound kind,
+    algorithmic bytes in the work slot), so bench.py's rooflines need no new category."""
+
+    @staticmethod
+    def forward(ctx, x, scale, shift):
+        _check(x, "film input")
+        if getattr(x, XSPLIT_ATTR, False) or getattr(x, BF16_ATTR, False):
+            raise RuntimeError("film: a pre-split / packed GroupNorm output holds no fp32 values; only a conv reads it")
+        lazy = getattr(x, GN_LAZY_ATTR, None)
+        if lazy is not None:  # a GroupNorm output deferred to a conv that is not coming: write it
+            x = lazy.materialize()
+        x, ldx = _pix(x)
+        n, c, h, w = x.shape
+        if tuple(scale.shape) != (n, c) or tuple(shift.shape) != (n, c):
+            raise ValueError(f"film: scale / shift must be [{n}, {c}], got {tuple(scale.shape)} / {tuple(shift.shape)}")
+        scale = scale.to(device=x.device, dtype=torch.float32).contiguous()
+        shift = shift.to(device=x.device, dtype=torch.float32).contiguous()
+        y = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32, memory_format=CL)
+        with _timed("gn_fwd", 8.0 * y.numel(), (n, c, h * w)):  # algorithmic HBM bytes: read x, write y
+            _lib.call("mvae_film_fwd", x.data_ptr(), ldx, scale.data_ptr(), shift.data_ptr(), y.data_ptr(), n, h * w, c,
+                      _stream(x))
+        ctx.save_for_backward(x, scale)
+        ctx.ldx = ldx
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, scale = ctx.saved_tensors
+        if not any(ctx.needs_input_grad):
+            return None, None, None
+        n, c, h, w = x.shape
+        dy, lddy = _pix(dy if dy.dtype == torch.float32 else dy.float())
+        want_dx = bool(ctx.needs_input_grad[0])
+        dx = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32, memory_format=CL) if want_dx else None
+        dscale = torch.empty((n, c), device=x.device, dtype=torch.float32)
+        dshift = torch.empty_like(dscale)
+        ws = ARENA.get("film", _lib.query("mvae_film_workspace_bytes", n, h * w, c), x.device)
+        # algorithmic HBM bytes: read x, dy; write dx unless skipped
+        with _timed("gn_bwd", (12.0 if want_dx else 8.0) * x.numel(), (n, c, h * w)):
+            _lib.call("mvae_film_bwd", x.data_ptr(), ctx.ldx, dy.data_ptr(), lddy, scale.data_ptr(), _ptr(dx),
+                      dscale.data_ptr(), dshift.data_ptr(), n, h * w, c, int(want_dx), ws.data_ptr(), ws.numel(),
+                      _stream(x))
+        return dx, (dscale if ctx.needs_input_grad[1] else None), (dshift if ctx.needs_input_grad[2] else None)
+
+
+def film(x, scale, shift):
+    """FiLM modulation x * scale[..., None, None] + shift[..., None, None] of a [B, C, H, W] feature map by per-sample,
+    per-channel scale / shift [B, C]. The result is a plain tensor: whatever a producer attached to x for a Normalize
+    that was to read it (the conv epilogue's GroupNorm statistics GN_PART_ATTR, its DyPack request, a backward link)
+    describes x, not the modulated map, and stays behind -- the next Normalize computes its own statistics, and the
+    producing conv, whose DyPack nobody fills, takes its output gradient as it comes. CPU tensors take plain torch."""
+    if not x.is_cuda:
+        return x * scale[..., None, None] + shift[..., None, None]
+    return FilmFn.apply(x, scale, shift)

@@ -126,11 +126,21 @@ class FiLMLayer(nn.Module):
 
 
 class ConditionalVAE(BaseVAE):
-    """Concat-conditioned VAE: one-hot -> Linear -> ReLU -> [C,8,8] -> bilinear -> concat with x."""
+    """VAE conditioned on a modality vector (one-hot by default), condition_method:
+      "concat"  one-hot -> Linear -> ReLU -> [C,8,8] -> bilinear -> concat with x (the encoder's input layer only)
+      "film"    one FiLMLayer per encoder level. As in the reference, its parameters exist and encode() ignores them
+                (conditional_vae.py: "TODO: Implement other conditioning methods") unless apply_film=True: then level
+                i's output is modulated by scale_transform_i(condition), shift_transform_i(condition) (FiLMLayer.forward,
+                fused: ops.film) before its downsample / the mid blocks
+      "inject"  parameters only, never used (as in the reference)
+    The decoder is unconditional."""
 
     def __init__(self, modalities: List[str] = None, condition_dim: int = None, condition_method: str = "concat",
-                 **kwargs):
+                 apply_film: bool = False, **kwargs):
         super().__init__(**kwargs)
+        self.apply_film = bool(apply_film)
+        if self.apply_film and condition_method != "film":
+            raise ValueError(f"apply_film=True needs condition_method='film', got {condition_method!r}")
         self.modalities = list(modalities) if modalities is not None else list(DEFAULT_MODALITIES)
         self.num_modalities = len(self.modalities)
         self.condition_dim = condition_dim or self.num_modalities
@@ -146,6 +156,13 @@ class ConditionalVAE(BaseVAE):
         elif condition_method == "film":
             self.film_layers = nn.ModuleList(
                 [FiLMLayer(self.condition_dim, self.encoder.ch * (2 ** i)) for i in range(len(self.encoder.down))])
+            if self.apply_film:
+                # the reference sizes layer i as ch * 2**i whatever ch_mult says; the layers are not resized
+                for i in range(len(self.encoder.down)):
+                    width, film_width = self.encoder.ch * self.encoder.in_ch_mult[i + 1], self.encoder.ch * (2 ** i)
+                    if width != film_width:
+                        raise ValueError(f"apply_film=True: encoder level {i} has {width} channels "
+                                         f"(ch * ch_mult[{i}]) but film_layers.{i} modulates {film_width} (ch * 2**{i})")
 
     def encode_condition(self, condition):
         return condition.unsqueeze(0) if condition.dim() == 1 else condition
@@ -165,6 +182,13 @@ class ConditionalVAE(BaseVAE):
             cmap = self.create_condition_map(condition.to(x.dtype), x.shape[2], x.shape[3])
             x_cond = torch.cat([x, cmap], dim=1).contiguous(memory_format=torch.channels_last)
             return super().encode(x_cond)
+        if self.apply_film:
+            cond = self.encode_condition(condition).to(x.dtype)
+            if cond.shape[0] != x.shape[0]:  # (one condition for the whole batch: FiLMLayer.forward broadcasts it)
+                cond = cond.expand(x.shape[0], -1)
+            film = [(layer.scale_transform(cond), layer.shift_transform(cond)) for layer in self.film_layers]
+            h = self.encoder(ops.nhwc(x), film=film)
+            return torch.chunk(h, 2, dim=1)
         return super().encode(x)
 
     def forward(self, x, condition, return_latents: bool = False, *, eps=None):
