@@ -208,6 +208,20 @@ int mvae_winograd_dy_transform(const float* dy, void* d, int nb, int h, int w, i
 // Replaces the two separate passes over dy of the conv backward (encoder_decoder.py ResnetBlock convs, autograd).
 int mvae_winograd_dy_transforms(const float* dy, void* v, void* d, int nb, int h, int w, int k, int dy_split, int tile,
                                 void* stream);
+/* mvae_winograd_dy_transforms of a dy that is never written: the input gradient of the GroupNorm(+SiLU) whose input x
+ * [nb][h][w][k] is this conv's output (no other consumer: ResnetBlock conv1 -> norm2), computed on load from x and
+ * that GroupNorm's upstream gradient dy with the coefficient rows of mvae_group_norm_bwd_part_coef_nhwc (coef, five
+ * rows coef_stride floats apart; img0: the launch's first image in them, for a conv run in image chunks). colsum
+ * [mvae_group_norm_bwd_dy_rows][k] fp32 receives per-workgroup column sums of dx; mvae_group_norm_bwd_dy_bias sums the
+ * rows of all chunks into the conv bias gradient (dbias = beta dbias + sums, fixed order: deterministic). The 3xBF16
+ * arithmetic's F(4x4) form with k / 4 a divisor of 256; mvae_group_norm_bwd_dy_rows is 0 for anything else. */
+int mvae_group_norm_bwd_dy_rows(int nb, int h, int w, int k, int tile);
+int mvae_group_norm_bwd_dy_transforms(const float* x, const float* dy, const float* coef, long long coef_stride,
+                                      int img0, int silu, void* v, void* d, float* colsum, int nb, int h, int w, int k,
+                                      int tile, void* stream);
+size_t mvae_group_norm_bwd_dy_bias_workspace_bytes(int k);
+int mvae_group_norm_bwd_dy_bias(const float* colsum, long long rows, int k, float* dbias, float beta, void* workspace,
+                                size_t workspace_bytes, void* stream);
 int mvae_winograd_wgrad_gemm(const void* d, const void* v, float* m, long long tiles, int cout, int cin, int tile,
                              float* workspace, size_t workspace_bytes, void* stream);
 int mvae_winograd_wgrad_output(const float* m, float* dw, float beta, int cout, int cin, int tile, void* stream);
@@ -388,6 +402,12 @@ int mvae_group_norm_bwd_part_split_nhwc(const float* x, const float* dy, const d
                                         int groups, int silu, void* workspace, size_t workspace_bytes, void* dx_split,
                                         float* dbias, float bias_beta, void* cs_workspace, size_t cs_workspace_bytes,
                                         void* stream);
+/* mvae_group_norm_bwd_part_nhwc without its dx pass: dgamma / dbeta and the coefficient rows coef [5][nb * c] (scale,
+ * shift, p, q, r per sample and channel: dx = p dyn + q x + r, dyn the gradient through SiLU at scale x + shift) for a
+ * consumer that computes dx where it reads it (mvae_group_norm_bwd_dy_transforms). Reads neither x nor dy. */
+int mvae_group_norm_bwd_part_coef_nhwc(const double* part, const float* gamma, const float* beta, const float* mean,
+                                       const float* rstd, float* dgamma, float* dbeta, int nb, int hw, int c,
+                                       int groups, void* workspace, size_t workspace_bytes, float* coef, void* stream);
 /* 1 when the GroupNorm backward of this geometry (with_dxp: its split / packed-output forms) runs the two-pass
  * streaming chain, whose partial pass the consuming conv can supply; 0 for the one-pass resident / unit kernels. */
 int mvae_group_norm_bwd_streaming(int nb, int hw, int c, int groups, int with_dxp);

@@ -43,6 +43,11 @@ SIGNATURES = {
     "mvae_winograd_output_gnbwd": (I, [P, P, P, P, P, P, P, I, I, P, I, I, I, I, I, P]),
     "mvae_winograd_dy_transform": (I, [P, P, I, I, I, I, I, I, P]),
     "mvae_winograd_dy_transforms": (I, [P, P, P, I, I, I, I, I, I, P]),
+    "mvae_group_norm_bwd_dy_rows": (I, [I, I, I, I, I]),
+    "mvae_group_norm_bwd_dy_transforms": (I, [P, P, P, L, I, I, P, P, P, I, I, I, I, I, P]),
+    "mvae_group_norm_bwd_dy_bias_workspace_bytes": (Z, [I]),
+    "mvae_group_norm_bwd_dy_bias": (I, [P, L, I, P, F, P, Z, P]),
+    "mvae_group_norm_bwd_part_coef_nhwc": (I, [P, P, P, P, P, P, P, I, I, I, I, P, Z, P, P]),
     "mvae_winograd_wgrad_gemm": (I, [P, P, P, L, I, I, I, P, Z, P]),
     "mvae_winograd_wgrad_output": (I, [P, P, F, I, I, I, P]),
     "mvae_winograd_upsample_weights": (I, [P, P, I, I, P]),

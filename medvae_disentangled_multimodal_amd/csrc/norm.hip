@@ -333,6 +333,24 @@ __global__ void __launch_bounds__(256) gn_bwd_finalize_kernel(GnArgs a, float* k
   }
 }
 
+// The backward as an elementwise map, per (sample, channel): with a = scale x + shift the forward's affine
+// (gn_stats_finalize_kernel's) and dyn the gradient through SiLU at a, dx = p dyn + q x + r -- five rows [nb][C],
+// `stride` floats apart: scale, shift, p = k1, q = k2 and r = k3 of the channel's group. For a consumer that computes
+// dx where it reads it (mvae_group_norm_bwd_dy_transforms) instead of gn_dx_kernel writing it.
+__global__ void __launch_bounds__(256) gn_bwd_coef_kernel(GnArgs a, const float* __restrict__ k1,
+                                                          const float* __restrict__ k2, const float* __restrict__ k3,
+                                                          float* __restrict__ coef, long long stride) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)a.nb * a.C) return;
+  const int b = (int)(i / a.C), c = (int)(i - (long long)b * a.C), bg = b * a.G + c / (a.C / a.G);
+  const float sc = a.rstd[bg] * a.gamma[c];
+  coef[i] = sc;
+  coef[stride + i] = a.beta[c] - a.mean[bg] * sc;
+  coef[2 * stride + i] = k1[i];
+  coef[3 * stride + i] = k2[bg];
+  coef[4 * stride + i] = k3[bg];
+}
+
 // dgamma[c] += sum_{b,chunks} s1 ; dbeta[c] += sum s0. Two fixed-order stages so the reduction over the
 // nb*chunks partial rows runs on many blocks: stage 1, block (channel tile, slice) sums its slice of rows
 // (64 channels x 4 row lanes per block) into part[slice][C][2]; stage 2 sums the slices per channel.
@@ -1434,7 +1452,7 @@ static int gn_bwd_part(const float* x, const float* dy, const double* part, cons
                        const float* mean, const float* rstd, float* dx, const float* dx_add, float* dgamma,
                        float* dbeta, int nb, int hw, int c, int groups, int silu, void* workspace,
                        size_t workspace_bytes, void* dx_split, float* dbias, float bias_beta, void* cs_ws,
-                       void* stream);
+                       void* stream, float* coef = nullptr);
 
 int mvae_group_norm_bwd_part_nhwc(const float* x, const float* dy, const double* part, const float* gamma,
                                   const float* beta, const float* mean, const float* rstd, float* dx,
@@ -1488,12 +1506,12 @@ static int gn_bwd_part(const float* x, const float* dy, const double* part, cons
                        const float* mean, const float* rstd, float* dx, const float* dx_add, float* dgamma,
                        float* dbeta, int nb, int hw, int c, int groups, int silu, void* workspace,
                        size_t workspace_bytes, void* dx_split, float* dbias, float bias_beta, void* cs_ws,
-                       void* stream) {
+                       void* stream, float* coef) {
   if (nb <= 0 || hw <= 0 || c <= 0 || (c & 3) || groups <= 0 || c % groups || hw % 32 || part == nullptr) {
     set_error("group_norm_bwd_part: needs hw %% 32 == 0 and C %% 4 == 0");
     return MVAE_EINVAL;
   }
-  if (dx == nullptr && dx_split == nullptr) {
+  if (dx == nullptr && dx_split == nullptr && coef == nullptr) {
     set_error("group_norm_bwd_part: dx may be null only when the split copy is written");
     return MVAE_EINVAL;
   }
@@ -1525,11 +1543,31 @@ static int gn_bwd_part(const float* x, const float* dy, const double* part, cons
     hipLaunchKernelGGL(gn_param_final_kernel, dim3(cdiv(c, 256)), dim3(256), 0, st, c, (const double*)pg, dgamma,
                        dbeta);
   }
+  if (coef) {  // (no dx pass: the consumer applies the coefficient rows where it reads dx)
+    hipLaunchKernelGGL(gn_bwd_coef_kernel, dim3(cdiv((long long)nb * c, 256)), dim3(256), 0, st, a, k1, k2, k3, coef,
+                       (long long)nb * c);
+    return launch_status();
+  }
   hipLaunchKernelGGL(gn_dx_kernel, dim3(a.chunks, nb), dim3(256), 0, st, a, k1, k2, k3, dx);
   if (dbias)
     hipLaunchKernelGGL(gn_colsum_final_kernel, dim3(cdiv(c, 16)), dim3(256), 0, st, (const double*)a.csp,
                        nb * a.chunks, c, dbias, bias_beta);
   return launch_status();
+}
+
+// mvae_group_norm_bwd_part_nhwc without its dx pass: dgamma / dbeta, and the backward's coefficient rows coef
+// [5][nb * c] (scale, shift, p, q, r: dx = p dyn + q x + r with dyn the gradient through SiLU at scale x + shift) for
+// a consumer that computes dx on load (mvae_group_norm_bwd_dy_transforms). Reads neither x nor dy.
+int mvae_group_norm_bwd_part_coef_nhwc(const double* part, const float* gamma, const float* beta, const float* mean,
+                                       const float* rstd, float* dgamma, float* dbeta, int nb, int hw, int c,
+                                       int groups, void* workspace, size_t workspace_bytes, float* coef,
+                                       void* stream) {
+  if (coef == nullptr || ((uintptr_t)coef & 15)) {
+    set_error("group_norm_bwd_part_coef: 16-B aligned coefficient rows");
+    return MVAE_EINVAL;
+  }
+  return gn_bwd_part(nullptr, nullptr, part, gamma, beta, mean, rstd, nullptr, nullptr, dgamma, dbeta, nb, hw, c, groups,
+                     0, workspace, workspace_bytes, nullptr, nullptr, 0.f, nullptr, stream, coef);
 }
 
 }  // extern "C"

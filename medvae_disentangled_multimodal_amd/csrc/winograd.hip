@@ -538,6 +538,11 @@ __global__ void __launch_bounds__(256) wino_out_any_kernel(WinoOut p) {
   }
 }
 
+template <int MT>
+__device__ __forceinline__ long long wino_tiles_dev(int nb, int H, int W) {
+  return (long long)nb * ((H + MT - 1) / MT) * ((W + MT - 1) / MT);
+}
+
 // Where the output-gradient 4-group k4 of low-resolution pixel (h, w) of image b lives (byte offset): the dy [nb][H][W][K]
 // of a conv; or, UPS (the Upsample conv run as 4 class convs on its low-resolution input, K = 4 cout, k4 = class pq x
 // cout / 4 + c4), the class-pq sub-image of the full-resolution dy [nb][2H][2W][cout] -- pixel (2h + p, 2w + q)
@@ -606,14 +611,26 @@ __global__ void __launch_bounds__(256) wino_dy_kernel(const float* __restrict__ 
 // D' = A D A^T of the m x m tile D = P[1..m][1..m] inside it (the weight gradient's transformed output gradient, as
 // wino_dy_kernel) -- the separate kernels each read all of dy. One thread per (tile, 4-group); D' one output row at a
 // time (181-215 VGPRs: the patch plus one row; 2 waves per SIMD, as the input transform).
-template <int MT, bool XS, int SF = 0, bool UPS = false>
-__global__ void __launch_bounds__(256) wino_dy2_kernel(const float* __restrict__ dy, uint4* __restrict__ v,
-                                                       uint4* __restrict__ d, int nb, int H, int W, int K) {
+//
+// GNB (1, 2 with SiLU): this conv's dy is the input gradient of a GroupNorm(+SiLU) whose input x is the conv's output
+// and has no other consumer (ResnetBlock conv1 -> norm2). It is computed on load from x and the GroupNorm's upstream
+// gradient `dy` and never written: a = scale x + shift, da = dy s (1 + a (1 - s)) with s = sigmoid(a) (da = dy without
+// SiLU), P = p da + q x + r, zero outside the image (coefficient rows of mvae_group_norm_bwd_part_coef_nhwc). The
+// workgroup's column sums of P's tiles (each pixel is in exactly one tile D) go to gb.colsum: the conv bias gradient.
+struct WinoGnb {
+  const float* x;     // the GroupNorm input [nb][H][W][K]
+  const float* coef;  // rows scale, shift, p, q, r, `stride` floats apart, each [images][K], at this launch's first image
+  long long stride;
+  float* colsum;      // [workgroups][K]
+};
+
+template <int MT, bool XS, int SF, bool UPS, int GNB>
+__device__ __forceinline__ float4 wino_dy2_tile(const float* __restrict__ dy, uint4* __restrict__ v,
+                                                uint4* __restrict__ d, int nb, int H, int W, int K, long long idx,
+                                                const WinoGnb& gb) {
   constexpr int AL = MT + 2;
   const int K4 = K >> 2, th = (H + MT - 1) / MT, tw = (W + MT - 1) / MT;
   const long long T = (long long)nb * th * tw;
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= T * K4) return;
   const long long t = idx / K4;
   const int k4 = (int)(idx - t * K4);
   const int tj = (int)(t % tw), ti = (int)((t / tw) % th), b = (int)(t / ((long long)tw * th));
@@ -632,6 +649,54 @@ __global__ void __launch_bounds__(256) wino_dy2_kernel(const float* __restrict__
       const float4 r = bload4(xr, ok ? src.off(h, w) : OOB);
       p[i][j] = XS ? split4_to_f32(r) : r;
     }
+  float4 bsum{0.f, 0.f, 0.f, 0.f};
+  if constexpr (GNB != 0) {
+    // x two patch rows at a time next to the whole dy patch (the two patches together would not leave two waves per
+    // SIMD their registers); branch-free after the loads, SiLU a template choice, as wino_in_kernel's GN
+    const __amdgpu_buffer_rsrc_t gr = make_rsrc(gb.x, (unsigned)((long long)nb * H * W * K * 4));
+    const float* cf = gb.coef + (long long)b * K + k4 * 4;
+    const float4 sc = *(const float4*)cf, sh = *(const float4*)(cf + gb.stride);
+    const float4 cp = *(const float4*)(cf + 2 * gb.stride), cq = *(const float4*)(cf + 3 * gb.stride);
+    const float4 cr = *(const float4*)(cf + 4 * gb.stride);
+    const float c1[4] = {sc.x, sc.y, sc.z, sc.w}, c2[4] = {sh.x, sh.y, sh.z, sh.w}, c3[4] = {cp.x, cp.y, cp.z, cp.w};
+    const float c4[4] = {cq.x, cq.y, cq.z, cq.w}, c5[4] = {cr.x, cr.y, cr.z, cr.w};
+#pragma unroll
+    for (int i0 = 0; i0 < AL; i0 += 2) {
+      float4 xv[2][AL];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < AL; ++j) {
+          const int h = MT * ti - 1 + i0 + i, w = MT * tj - 1 + j;
+          const bool ok = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+          xv[i][j] = bload4(gr, ok ? src.off(h, w) : OOB);
+        }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < AL; ++j) {
+          const int h = MT * ti - 1 + i0 + i, w = MT * tj - 1 + j;
+          const bool ok = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+          const float xs[4] = {xv[i][j].x, xv[i][j].y, xv[i][j].z, xv[i][j].w};
+          const float4 g = p[i0 + i][j];
+          float o[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if constexpr (GNB == 2) {
+              const float a = fmaf(xs[e], c1[e], c2[e]);
+              const float s = __builtin_amdgcn_rcpf(1.f + __expf(-a));
+              o[e] = o[e] * (s * fmaf(a, 1.f - s, 1.f));
+            }
+            o[e] = fmaf(c3[e], o[e], fmaf(c4[e], xs[e], c5[e]));
+          }
+          p[i0 + i][j] = ok ? float4{o[0], o[1], o[2], o[3]} : float4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < MT; ++u)
+#pragma unroll
+      for (int e = 0; e < MT; ++e) bsum = f4add(bsum, p[1 + u][1 + e]);
+  }
 #pragma unroll
   for (int i = 0; i < AL; ++i) {  // D' row i = (A D)[i] A^T, A[i][u] = A^T[u][i]
     float4 ci[MT], o[AL];
@@ -661,6 +726,34 @@ __global__ void __launch_bounds__(256) wino_dy2_kernel(const float* __restrict__
   for (int i = 0; i < AL; ++i)
 #pragma unroll
     for (int j = 0; j < AL; ++j) wstore_f<SF>(vr, base + (unsigned)(i * AL + j) * plane, p[i][j]);
+  return bsum;
+}
+
+template <int MT, bool XS, int SF = 0, bool UPS = false>
+__global__ void __launch_bounds__(256) wino_dy2_kernel(const float* __restrict__ dy, uint4* __restrict__ v,
+                                                       uint4* __restrict__ d, int nb, int H, int W, int K) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= wino_tiles_dev<MT>(nb, H, W) * (K >> 2)) return;
+  wino_dy2_tile<MT, XS, SF, UPS, 0>(dy, v, d, nb, H, W, K, idx, WinoGnb{});
+}
+
+// the GroupNorm-backward-on-load form (K / 4 divides 256: a workgroup is whole tiles x all the 4-groups, thread tid's
+// 4-group is tid % (K / 4)); the tiles' column sums are added in tile order through LDS, one row of K per workgroup
+template <int MT, int SF, int GNB>
+__global__ void __launch_bounds__(256) wino_dy2_gnb_kernel(const float* __restrict__ dy, uint4* __restrict__ v,
+                                                           uint4* __restrict__ d, int nb, int H, int W, int K,
+                                                           WinoGnb gb) {
+  __shared__ float4 red[256];
+  const int tid = threadIdx.x, K4 = K >> 2;
+  const long long idx = (long long)blockIdx.x * blockDim.x + tid;
+  float4 bs{0.f, 0.f, 0.f, 0.f};
+  if (idx < wino_tiles_dev<MT>(nb, H, W) * K4) bs = wino_dy2_tile<MT, false, SF, false, GNB>(dy, v, d, nb, H, W, K, idx, gb);
+  red[tid] = bs;
+  __syncthreads();
+  if (tid < K4) {
+    for (int q = tid + K4; q < 256; q += K4) bs = f4add(bs, red[q]);
+    *(float4*)(gb.colsum + (long long)blockIdx.x * K + tid * 4) = bs;
+  }
 }
 
 // The Upsample conv (nearest x2, then a 3x3 / pad-1 conv: encoder_decoder.py:194-209) as four 3x3 / pad-1 convs on the
@@ -893,6 +986,47 @@ static void dy_go(const float* dy, void* v, void* d, int nb, int h, int w, int k
   }
   if (both) hipLaunchKernelGGL((wino_dy2_kernel<MT, false, SF>), g, dim3(256), 0, st, dy, vv, dd, nb, h, w, k);
   else hipLaunchKernelGGL((wino_dy_kernel<MT, false, SF>), g, dim3(256), 0, st, dy, dd, nb, h, w, k);
+}
+
+// workgroups of wino_dy2_gnb_kernel = rows of its column-sum partials; 0: no such form (it needs K / 4 to divide 256)
+static long long dy_gnb_rows(int nb, int h, int w, int k, int mt) {
+  const int k4 = k / 4;
+  return (k4 > 0 && k4 <= 256 && 256 % k4 == 0) ? (wino_tiles(nb, h, w, mt) * k4 + 255) / 256 : 0;
+}
+
+template <int MT, int SF>
+static void dy_gnb_go(const float* dy, void* v, void* d, int nb, int h, int w, int k, int silu, WinoGnb gb,
+                      hipStream_t st) {
+  const dim3 g((unsigned)dy_gnb_rows(nb, h, w, k, MT));
+  if (silu) hipLaunchKernelGGL((wino_dy2_gnb_kernel<MT, SF, 2>), g, dim3(256), 0, st, dy, (uint4*)v, (uint4*)d, nb, h, w, k, gb);
+  else hipLaunchKernelGGL((wino_dy2_gnb_kernel<MT, SF, 1>), g, dim3(256), 0, st, dy, (uint4*)v, (uint4*)d, nb, h, w, k, gb);
+}
+
+// The conv bias gradient from wino_dy2_gnb_kernel's column-sum partials part [rows][K] (fp32), in two fixed-order fp64
+// stages (deterministic): slice sl of WCS_SLICES sums its rows per channel (64 channels x 4 row lanes per workgroup,
+// the lanes added in order), then out[c] = beta out[c] + the slices in order.
+constexpr int WCS_SLICES = 64;
+__global__ void __launch_bounds__(256) wino_colsum_slice_kernel(const float* __restrict__ part, long long rows, int K,
+                                                                double* __restrict__ sl_out) {
+  __shared__ double sh[256];
+  const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl, sl = blockIdx.y;
+  const long long lo = rows * sl / WCS_SLICES, hi = rows * (sl + 1) / WCS_SLICES;
+  double s = 0.0;
+  if (c < K)
+    for (long long i = lo + rg; i < hi; i += 4) s += (double)part[i * K + c];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  if (rg == 0 && c < K) sl_out[(long long)sl * K + c] = sh[cl] + sh[cl + 64] + sh[cl + 128] + sh[cl + 192];
+}
+
+__global__ void __launch_bounds__(256) wino_colsum_final_kernel(const double* __restrict__ sl_in, int K,
+                                                                float* __restrict__ out, float beta) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= K) return;
+  double s = 0.0;
+  for (int sl = 0; sl < WCS_SLICES; ++sl) s += sl_in[(long long)sl * K + c];
+  out[c] = (beta != 0.f ? beta * out[c] : 0.f) + (float)s;
 }
 
 template <int MT, int WSEG>
@@ -1136,6 +1270,53 @@ int mvae_winograd_dy_transforms(const float* dy, void* v, void* d, int nb, int h
   const int sf = wino_sf();
   if (tile == 2) WINO_GO(dy_go, 2, dy, v, d, nb, h, w, k, dy_split, true, st);
   else WINO_GO(dy_go, 4, dy, v, d, nb, h, w, k, dy_split, true, st);
+  return launch_status();
+}
+
+// mvae_winograd_dy_transforms of a dy that is never written: the input gradient dx of the GroupNorm(+SiLU) whose input
+// x [nb][h][w][k] is this conv's output, computed on load from x and that GroupNorm's upstream gradient dy
+// (wino_dy2_tile's GNB form). coef: mvae_group_norm_bwd_part_coef_nhwc's five rows [images][k], coef_stride floats
+// apart; img0 the first image of this launch in them (a conv run in image chunks). colsum [rows][k] fp32 receives the
+// workgroups' column sums of dx, rows = mvae_group_norm_bwd_dy_rows (the conv bias gradient:
+// mvae_group_norm_bwd_dy_bias over the rows of every chunk). The 3xBF16 arithmetic's F(4x4) form only.
+int mvae_group_norm_bwd_dy_rows(int nb, int h, int w, int k, int tile) {
+  // (at most 2^30 / 256 rows: wino_geom_ok bounds tiles x k)
+  return (tile == 4 && wino_sf() == 0 && wino_geom_ok(tile, nb, h, w, k, k)) ? (int)dy_gnb_rows(nb, h, w, k, tile) : 0;
+}
+
+int mvae_group_norm_bwd_dy_transforms(const float* x, const float* dy, const float* coef, long long coef_stride,
+                                      int img0, int silu, void* v, void* d, float* colsum, int nb, int h, int w, int k,
+                                      int tile, void* stream) {
+  if (!x || !dy || !coef || !v || !d || !colsum || img0 < 0 || coef_stride < (long long)(img0 + nb) * k ||
+      coef_stride % 4 || !al16(x) || !al16(dy) || !al16(coef) || !al16(v) || !al16(d) || !al16(colsum) ||
+      mvae_group_norm_bwd_dy_rows(nb, h, w, k, tile) <= 0) {
+    set_error("group_norm_bwd_dy_transforms: the 3xBF16 arithmetic, tile 4, k / 4 a divisor of 256, 16-B aligned, "
+              "coefficient rows covering the images");
+    return MVAE_EINVAL;
+  }
+  const WinoGnb gb{x, coef + (long long)img0 * k, coef_stride, colsum};
+  dy_gnb_go<4, 0>(dy, v, d, nb, h, w, k, silu, gb, (hipStream_t)stream);
+  return launch_status();
+}
+
+// dbias[c] = beta dbias[c] + the column sums of `rows` partial rows of mvae_group_norm_bwd_dy_transforms (fixed order)
+size_t mvae_group_norm_bwd_dy_bias_workspace_bytes(int k) { return (size_t)WCS_SLICES * std::max(k, 0) * sizeof(double); }
+
+int mvae_group_norm_bwd_dy_bias(const float* colsum, long long rows, int k, float* dbias, float beta, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  if (!colsum || !dbias || !workspace || rows <= 0 || k <= 0 || ((uintptr_t)workspace & 7)) {
+    set_error("group_norm_bwd_dy_bias: partial rows, a bias gradient and an 8-B aligned workspace");
+    return MVAE_EINVAL;
+  }
+  if (workspace_bytes < mvae_group_norm_bwd_dy_bias_workspace_bytes(k)) {
+    set_error("group_norm_bwd_dy_bias: workspace too small");
+    return MVAE_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(wino_colsum_slice_kernel, dim3(cdiv(k, 64), WCS_SLICES), dim3(256), 0, st, colsum, rows, k,
+                     (double*)workspace);
+  hipLaunchKernelGGL(wino_colsum_final_kernel, dim3(cdiv(k, 256)), dim3(256), 0, st, (const double*)workspace, k, dbias,
+                     beta);
   return launch_status();
 }
 

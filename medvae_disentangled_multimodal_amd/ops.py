@@ -400,15 +400,73 @@ class DeferredGnOutput(torch.Tensor):
     checks) pass; ops.conv2d takes the values from the LazyGn record it carries. MVAE_NO_WINOGRAD_GN=1 writes the
     GroupNorm output instead."""
 
+    _READ_MSG = ("this GroupNorm output is deferred to its consuming convolution (the conv's Winograd input transform "
+                 "applies the normalization); its values exist nowhere else. Read the conv's output instead, or set "
+                 "MVAE_NO_WINOGRAD_GN=1 to have the GroupNorm write its output.")
+
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
         if func in _DEFERRED_META:
             with torch._C.DisableTorchFunctionSubclass():
                 return func(*args, **(kwargs or {}))
         name = getattr(func, "__qualname__", None) or getattr(func, "__name__", repr(func))
-        raise RuntimeError(f"{name}: this GroupNorm output is deferred to its consuming convolution (the conv's Winograd "
-                           "input transform applies the normalization); its values exist nowhere else. Read the conv's "
-                           "output instead, or set MVAE_NO_WINOGRAD_GN=1 to have the GroupNorm write its output.")
+        raise RuntimeError(f"{name}: {cls._READ_MSG}")
+
+
+# ... and the mirror image in the backward pass. A GroupNorm whose input is a conv output with no other consumer
+# (ResnetBlock norm2 of conv1's output) has one reader of its input gradient: that conv's backward, in its one pass over
+# dy (mvae_winograd_dy_transforms). Where the GroupNorm backward would stream (partials from the consuming conv,
+# WINOGRAD_GN_LINK; then gn_dx_kernel: read x and dy, write dx) it computes only its coefficient rows
+# (mvae_group_norm_bwd_part_coef_nhwc) and hands the producing conv a DeferredGnGrad; that conv's dy transform computes
+# dx from x and the GroupNorm's upstream gradient on load (mvae_group_norm_bwd_dy_transforms, branch-free, SiLU a
+# template choice as in the forward) and sums the conv bias gradient per workgroup. dx is never written or read back:
+# 8 of 16 B per element. Only the 3xBF16 F(4x4) form with both gradients on the Winograd path (ConvPlan.gnb_on_load);
+# anything else -- retain_grad or a hook on the conv output, a second backward over a retained graph, another math mode
+# -- writes dx with gn_dx_kernel as before. profiles/gnbwd_load_ab.txt. MVAE_NO_WINOGRAD_GNBWD_LOAD=1: always written.
+WINOGRAD_GNBWD_LOAD = os.environ.get("MVAE_NO_WINOGRAD_GNBWD_LOAD") is None
+GNB_LAZY_ATTR = "_mvae_gnb_lazy"
+
+
+class LazyGnGrad:
+    """A GroupNorm input gradient deferred to the conv that produced the GroupNorm's input: x (that input), dy (the
+    GroupNorm's upstream gradient), the backward's coefficient rows coef [5][n * c] and the SiLU flag; part and the
+    GroupNorm's parameters and statistics so that materialize() can still write dx (and the conv bias gradient) with the
+    GroupNorm's own dx pass for a conv backward that cannot compute it on load."""
+    __slots__ = ("x", "dy", "coef", "silu", "part", "gamma", "beta", "mean", "rstd", "groups", "colsum")
+
+    def __init__(self, x, dy, coef, silu, part, gamma, beta, mean, rstd, groups):
+        self.x, self.dy, self.coef, self.silu, self.part = x, dy, coef, int(silu), part
+        self.gamma, self.beta, self.mean, self.rstd, self.groups = gamma, beta, mean, rstd, groups
+        self.colsum = None  # (the dy transforms' column-sum partials and their row count, once they ran)
+
+    def materialize(self):
+        x = self.x
+        n, c, h, w = x.shape
+        dx = torch.empty_like(x, memory_format=CL)
+        db = torch.empty(c, device=x.device, dtype=torch.float32)
+        ws = ARENA.get("gn", _lib.query("mvae_group_norm_workspace_bytes", n, h * w, c), x.device)
+        cs = ARENA.get("gncs", _lib.query("mvae_group_norm_colsum_workspace_bytes", n, h * w, c), x.device)
+        _lib.call("mvae_group_norm_bwd_part_split_nhwc", x.data_ptr(), self.dy.data_ptr(), self.part.data_ptr(),
+                  self.gamma.data_ptr(), self.beta.data_ptr(), self.mean.data_ptr(), self.rstd.data_ptr(),
+                  dx.data_ptr(), None, None, None, n, h * w, c, self.groups, self.silu, ws.data_ptr(), ws.numel(), None,
+                  db.data_ptr(), 0.0, cs.data_ptr(), cs.numel(), _stream(x))
+        return dx, db
+
+
+class DeferredGnGrad(DeferredGnOutput):
+    """The placeholder a GroupNorm backward returns for a deferred input gradient (LazyGnGrad, GNB_LAZY_ATTR): shape,
+    dtype and device of dx, no values. Only the producing conv's backward takes it; any read raises."""
+    _READ_MSG = ("this GroupNorm input gradient is deferred to the backward of the convolution that produced the "
+                 "GroupNorm's input (its Winograd dy transform computes it on load); its values exist nowhere else. Set "
+                 "MVAE_NO_WINOGRAD_GNBWD_LOAD=1 to have the GroupNorm backward write it.")
+
+
+def _engine_runs(node) -> bool:
+    """Whether the running backward pass executes this autograd node (False outside a pass, or when it cannot say)."""
+    try:
+        return node is not None and bool(torch._C._will_engine_execute_node(node))
+    except Exception:
+        return False
 
 
 _DEFERRED_META = {torch.Tensor.shape.__get__, torch.Tensor.size, torch.Tensor.dim, torch.Tensor.ndim.__get__,
@@ -433,13 +491,14 @@ WINOGRAD_KEEP_V = os.environ.get("MVAE_NO_WINOGRAD_KEEP_V") is None
 
 
 def _winograd(src, w, n: int, h: int, wd: int, k_in: int, n_out: int, src_split: bool, dgrad: bool, st, keep=None,
-              gn=None, key=None, u=None, chunk=(0, 0), dkeep=None):
+              gn=None, key=None, u=None, chunk=(0, 0), dkeep=None, gnb=None):
     """U (filters, unless `u` is given), V (input tiles) and the (m+2)^2 position GEMMs M = V U^T for the n images of
     src; returns (M (arena), U) for an output transform. keep (a list): V is allocated outside the arena and appended
     to it (WINOGRAD_KEEP_V), tagged with `key` (the conv's input tensor; default src) and the image range `chunk`.
     gn (LazyGn): src is a GroupNorm input, normalized on load (its scale / shift rows of these images).
     dkeep (a list; input gradient only): src is dy, and the weight gradient's D' = A dy A^T comes out of the same pass
-    over dy (mvae_winograd_dy_transforms), appended like keep's entries for conv2d_wgrad_raw."""
+    over dy (mvae_winograd_dy_transforms), appended like keep's entries for conv2d_wgrad_raw.
+    gnb ((LazyGnGrad, column-sum rows of this chunk); with dkeep): dy is a GroupNorm input gradient computed on load."""
     mt = _wtile()
     t = _wino_tiles(n, h, wd)
     pos = (mt + 2) ** 2
@@ -457,8 +516,15 @@ def _winograd(src, w, n: int, h: int, wd: int, k_in: int, n_out: int, src_split:
     if dkeep is not None:
         d = torch.empty(_wel() * pos * t * k_in, dtype=torch.uint8, device=dev)
         dkeep.append(_Kept(d, mt, kt.data_ptr(), kt._version, tuple(chunk)))
-        _lib.call("mvae_winograd_dy_transforms", src.data_ptr(), v.data_ptr(), d.data_ptr(), n, h, wd, k_in,
-                  int(src_split), mt, st)
+        if gnb is not None:  # src stands in for a dy that was never written: computed on load (LazyGnGrad)
+            rec, cs = gnb
+            b0 = chunk[0]
+            _lib.call("mvae_group_norm_bwd_dy_transforms", rec.x[b0:b0 + n].data_ptr(), rec.dy[b0:b0 + n].data_ptr(),
+                      rec.coef.data_ptr(), rec.coef.numel() // 5, b0, rec.silu, v.data_ptr(), d.data_ptr(),
+                      cs.data_ptr(), n, h, wd, k_in, mt, st)
+        else:
+            _lib.call("mvae_winograd_dy_transforms", src.data_ptr(), v.data_ptr(), d.data_ptr(), n, h, wd, k_in,
+                      int(src_split), mt, st)
     elif gn is not None:
         b0 = chunk[0]
         _lib.call("mvae_winograd_input_transform_gn", src.data_ptr(), gn.scale[b0 * k_in:].data_ptr(),
@@ -813,6 +879,7 @@ class ConvPlan:
     dy_copy_ok: bool  # every backward family reads the packed / split copy, never the fp32 dy
     dy_pack: bool     # the conv backward packs dy itself for its GEMMs (pack_dy)
     gn_on_load: bool  # the forward can normalize a GroupNorm input on load and the weight gradient never reads x
+    gnb_on_load: bool = False  # the backward's one pass over dy can compute a producing GroupNorm's dx on load (LazyGnGrad)
 
     def alg(self, family: str) -> float:
         if family in ("wino", "wino_ups"):
@@ -870,7 +937,12 @@ def plan_conv(g: ConvGeom, n: int, c: int, h: int, w: int, cout: int, math_mode:
         chunks = tuple(_wino_chunks(n, h, w, max(c, 4 * co if wino == "wino_ups" else co))) if wino else ()
         return ConvPlan(g, n, c, h, w, co, math, (n, c, h, w, co, g.kh, g.stride, ups), wino, fwd, dgrad, wgrad, _wtile(), _wel(), chunks, _wino_blocks(h, w),
                         2.0 * macs, dy_format, dy_bias, copy_ok, dy_pack,
-                        bool(WINOGRAD_GN and WINOGRAD_WGRAD and wino == "wino"))
+                        bool(WINOGRAD_GN and WINOGRAD_WGRAD and wino == "wino"),
+                        # (the 3xBF16 F(4x4) form, both gradients planned on the Winograd path off one pass over dy, a
+                        # workgroup of the transform whole tiles: cout / 4 a divisor of 256)
+                        bool(WINOGRAD_GNBWD_LOAD and WINOGRAD_DY2 and math == 0 and _wtile() == 4 and
+                             dgrad[:1] == ("wino",) and wgrad[:1] == ("wino",) and dy_format == "bias" and
+                             co % 4 == 0 and 256 % (co // 4) == 0))
     finally:
         _MATH[0] = prev
 
@@ -1072,13 +1144,16 @@ def split_dy(dy: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=None, dkeep=None, out=None,
-                     beta: float = 0.0, plan: Optional[ConvPlan] = None):
+                     beta: float = 0.0, plan: Optional[ConvPlan] = None, gnb=None):
     """gn_link (GnBwdLink): the conv's input was silu?(GroupNorm(x)) -- also emit that GroupNorm's backward
     partials from the GEMM epilogue (mvae_conv2d_dgrad_gnbwd_nhwc) into gn_link.part when the launch allows it.
     dys: dy pre-split by split_dy (same values; used as the gathered GEMM operand when given).
     dyb: dy as packed bf16 (pack_dy; bf16-mixed mode).
     dkeep (a list): on the Winograd path also keep the weight gradient's transformed dy per image chunk (_winograd).
-    out / beta (1x1 convs only): dx = beta * out + dy W into out (DxSum)."""
+    out / beta (1x1 convs only): dx = beta * out + dy W into out (DxSum).
+    gnb (LazyGnGrad; with dkeep, Winograd only): dy's values were never written -- dy is the GroupNorm's upstream gradient
+    standing in for shape and keys, and the one pass over dy computes them on load; gnb.colsum receives the column-sum
+    partials of the conv bias gradient."""
     n, c, h, wd = x_shape
     co = w.shape[0]
     _, _, ho, wo = dy.shape
@@ -1092,6 +1167,8 @@ def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=No
         dys = None
     dya = dy if dys is None else dys
     fam = _dgrad_family(p, dy, w, dx, gn_link, dys, dyb)
+    if gnb is not None and fam != "wino":
+        raise RuntimeError("conv2d dgrad: a deferred GroupNorm input gradient reached a kernel that reads dy")
     mt, pos = p.tile, (p.tile + 2) ** 2
     dma = fam == "dma"  # the launches below on packed bf16 (planar) dy and weights, staged into LDS by DMA
     if dma:
@@ -1135,10 +1212,17 @@ def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=No
             L = gn_link if gn_link is not None and gn_link.usable(dx) and p.blocks else None
             part = torch.empty(n * h * wd // 32 * c * 2, device=dy.device, dtype=torch.float64) if L else None
             u = None
-            for b0, b1 in p.chunks:
+            if gnb is not None:  # column-sum partials of the on-load dy (the bias gradient): every chunk's rows in one buffer
+                rows = [_lib.query("mvae_group_norm_bwd_dy_rows", b1 - b0, h, wd, co, mt) for b0, b1 in p.chunks]
+                if dkeep is None or dys is not None or min(rows) <= 0:
+                    raise RuntimeError("conv2d dgrad: no one-pass dy transform for a deferred GroupNorm input gradient")
+                cs = ARENA.get("wino_cs", 4 * sum(rows) * co, dy.device)
+                gnb.colsum = (cs, sum(rows))
+            for i, (b0, b1) in enumerate(p.chunks):
                 nb = b1 - b0
                 m, u = _winograd(dya[b0:b1], w, nb, h, wd, co, c, dys is not None, True, st, u=u, key=dya,
-                                 chunk=(b0, b1), dkeep=dkeep)
+                                 chunk=(b0, b1), dkeep=dkeep,
+                                 gnb=None if gnb is None else (gnb, cs[4 * sum(rows[:i]) * co:]))
                 if L is None:
                     _lib.call("mvae_winograd_output_transform", m.data_ptr(), None, None, dx[b0:b1].data_ptr(), None, nb,
                               h, wd, c, mt, st)
@@ -1179,15 +1263,21 @@ def conv2d_dgrad_raw(dy, w, x_shape, g: ConvGeom, gn_link=None, dys=None, dyb=No
 
 
 def conv2d_wgrad_raw(dy, x, dw, beta: float, g: ConvGeom, db=None, x_split: bool = False, dys=None, dyb=None,
-                     x_bf16: bool = False, wino_v=None, wino_d=None, lazy=None, plan: Optional[ConvPlan] = None):
+                     x_bf16: bool = False, wino_v=None, wino_d=None, lazy=None, plan: Optional[ConvPlan] = None,
+                     dy_deferred: bool = False):
     """dw (+ db when given and the conv is not pointwise) accumulate with `beta`. Returns True when
     the bias gradient was produced by the fused wgrad kernel. dys: dy pre-split by split_dy; dyb: dy as packed bf16
     (pack_dy, bf16-mixed mode). lazy (LazyGn): x is a deferred GroupNorm output -- the Winograd weight gradient takes
-    the forward's kept V (or re-derives it from the GroupNorm input); any other weight gradient gets x written first."""
+    the forward's kept V (or re-derives it from the GroupNorm input); any other weight gradient gets x written first.
+    dy_deferred: dy only stands in for a gradient that was never written (LazyGnGrad) -- the Winograd form on the D' kept
+    by the input gradient's pass (wino_d) is the only way, anything that would read dy raises."""
     n, c, h, wd = x.shape
     _, co, ho, wo = dy.shape
     p = plan if plan is not None else plan_conv(g, n, c, h, wd, co, _MATH[0])
     fam = _wgrad_family(p, x, dy, dw, db, x_split, dys, dyb, lazy)
+    if dy_deferred and (fam != "wino" or dys is not None or
+                        set(_kept(wino_d, p.tile, dy)) != set(tuple(ch) for ch in p.chunks)):
+        raise RuntimeError("conv2d wgrad: a deferred GroupNorm input gradient reached a kernel that reads dy")
     if lazy is not None and fam != "wino":
         x, lazy = lazy.materialize(), None
         fam = _wgrad_family(p, x, dy, dw, db, x_split, dys, dyb, None)
@@ -1361,7 +1451,7 @@ DYSPLIT_MIN_MACS = 1e11
 
 class DyPack:
     __slots__ = ("bias_ref", "packed", "dx_ref", "dx_version", "dx_shape", "bias_done", "db", "fmt", "nodx",
-                 "copy_ok")
+                 "copy_ok", "defer_ok", "deferred")
 
     def __init__(self, bias_ref, fmt: str = "packed", copy_ok: bool = False):
         self.bias_ref = bias_ref
@@ -1372,6 +1462,17 @@ class DyPack:
         self.bias_done = False
         self.nodx = False  # the GroupNorm wrote only the copy (its dx has this conv as its only consumer)
         self.copy_ok = copy_ok  # (ConvPlan.dy_copy_ok: every backward family of the conv reads the copy)
+        # the conv's backward can compute the GroupNorm's dx on load (set by Conv2dFn.forward: ConvPlan.gnb_on_load and
+        # both gradients wanted), and the DeferredGnGrad placeholder the GroupNorm backward then returned instead of dx
+        self.defer_ok = False
+        self.deferred = None
+
+    def take_deferred(self, dy):
+        """The LazyGnGrad record, when dy is exactly the placeholder the GroupNorm backward returned; consumed once."""
+        ph, self.deferred = self.deferred, None
+        if ph is None or not isinstance(dy, DeferredGnGrad) or dy.data_ptr() != ph.data_ptr():
+            return None
+        return getattr(ph, GNB_LAZY_ATTR, None)
 
     def take(self, dy):
         """(packed dy, bias gradient done, returned bias gradient) when the GroupNorm backward produced them from
@@ -1379,6 +1480,10 @@ class DyPack:
         tracked by a weak reference, not its address: once autograd has summed another branch into a new tensor and
         freed dx, that address can come back from the allocator for an unrelated dy (a layout copy of the sum) --
         a stale address match the weak reference rules out."""
+        if self.deferred is not None:
+            self.deferred = None
+            raise RuntimeError("conv2d backward: the GroupNorm deferred its input gradient to this conv (its only consumer), "
+                               "but the conv's output gradient is another tensor")
         packed, ref, ver, shp, nodx = self.packed, self.dx_ref, self.dx_version, self.dx_shape, self.nodx
         out = (packed, self.bias_done, self.db)
         self.packed = self.dx_ref = self.dx_version = self.dx_shape = self.db = None
@@ -1457,6 +1562,9 @@ class Conv2dFn(torch.autograd.Function):
         ctx.gn_link = gn_link
         ctx.dx_sum = dx_sum
         ctx.dypack = dypack
+        if dypack is not None:
+            dypack.defer_ok = bool(grad_on and plan.gnb_on_load and ctx.needs_input_grad[0] and
+                                   ctx.needs_input_grad[1] and residual is None and dx_sum is None and _al16(w))
         return y
 
     @staticmethod
@@ -1468,6 +1576,20 @@ class Conv2dFn(torch.autograd.Function):
     def _backward(ctx, dy):
         x, w = ctx.saved_tensors
         g, plan = ctx.geom, ctx.plan
+        gnb = got = None
+        if isinstance(dy, DeferredGnGrad):
+            # the GroupNorm on this conv's output never wrote its dx: the one pass over dy below computes it on load from
+            # the GroupNorm's input and upstream gradient (which stands in as dy for shapes and keys), or -- a switch or
+            # the weights' layout changed since the forward -- the GroupNorm's own dx pass writes it now
+            gnb = ctx.dypack.take_deferred(dy) if ctx.dypack is not None else None
+            if gnb is None:
+                raise RuntimeError("conv2d backward: a deferred GroupNorm input gradient that is not this conv's")
+            if (WINOGRAD_GNBWD_LOAD and WINOGRAD_DY2 and plan.gnb_on_load and _wgrad_wino_on(plan) and _al16(w) and
+                    ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ctx.has_res and ctx.dx_sum is None):
+                dy = gnb.dy
+            else:
+                dy, dbm = gnb.materialize()
+                gnb, got = None, (True, True, dbm)
         dy = nhwc(dy)
         dx = dw_ret = db_ret = dres = None
         link = ctx.gn_link
@@ -1476,7 +1598,8 @@ class Conv2dFn(torch.autograd.Function):
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         bias_done = False
         dyb = None
-        got = ctx.dypack.take(dy) if ctx.dypack is not None else None
+        if got is None and gnb is None and ctx.dypack is not None:
+            got = ctx.dypack.take(dy)
         dys = None
         if got is not None:  # from the GroupNorm backward that produced dy: the bias gradient (column sums of its dx)
             taken, bias_done, db_ret = got
@@ -1491,7 +1614,7 @@ class Conv2dFn(torch.autograd.Function):
                 if bt is not None:  # into the flat slot now that dy is known to be the GroupNorm's dx
                     bt.add_(db_ret)
                     db_ret = None
-        elif ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        elif gnb is None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             # bf16-mixed: pack dy once for both GEMMs; the bias gradient comes out of the same pass
             bt = _main_grad(ctx.bias_ref) if want_b else None
             if want_b and bt is None:
@@ -1500,7 +1623,7 @@ class Conv2dFn(torch.autograd.Function):
                                      plan)
             if not bias_done:
                 db_ret = None
-        if dys is None and not g.pointwise and not _subpixel_upsample(g) and dyb is None:
+        if dys is None and not g.pointwise and not _subpixel_upsample(g) and dyb is None and gnb is None:
             dys = split_dy(dy)
         dkeep = None  # (set below when the input gradient's pass over dy also writes the weight gradient's D')
 
@@ -1513,11 +1636,12 @@ class Conv2dFn(torch.autograd.Function):
             btgt = _main_grad(ctx.bias_ref) if tgt is not None and want_b and not bias_done else None
             fused = conv2d_wgrad_raw(dy, x, dw_ret if tgt is None else tgt, 0.0 if tgt is None else 1.0, g, btgt,
                                      x_split=ctx.x_split, dys=dys, dyb=dyb, x_bf16=ctx.x_bf16, wino_v=ctx.wino_v,
-                                     wino_d=dkeep, lazy=ctx.lazy, plan=plan)
+                                     wino_d=dkeep, lazy=ctx.lazy, plan=plan, dy_deferred=gnb is not None)
             bias_done = bias_done or fused
 
         # (image-side convs -- cout 3 / latent channels -- run memory-bound special kernels: c4 lost 0.35 % overlapping them)
-        side = _bwd_side(dy) if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and \
+        # (a dy computed on load has one pass over it for both gradients: no side stream)
+        side = _bwd_side(dy) if gnb is None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and \
             _main_grad(ctx.weight_ref) is not None and not g.pointwise and min(plan.c, plan.co) >= 32 and \
             plan.ref <= BWD_OVERLAP_MAX_FLOPS else None
         if side is not None:
@@ -1550,9 +1674,20 @@ class Conv2dFn(torch.autograd.Function):
                 dx, acc.buf, acc.left = acc.buf, None, acc.n
         elif ctx.needs_input_grad[0]:
             dx = conv2d_dgrad_raw(dy, w, x.shape, g, link if ctx.x_sink is None else None, dys=dys, dyb=dyb,
-                                  dkeep=dkeep, plan=plan)
+                                  dkeep=dkeep, plan=plan, gnb=gnb)
             if ctx.x_sink is not None and ctx.x_sink.park(dx):
                 dx = None
+            if gnb is not None and want_b:
+                # the bias gradient: the transforms' per-workgroup column sums of the on-load dy, in fixed order
+                cs, rows = gnb.colsum
+                bt = _main_grad(ctx.bias_ref)
+                if bt is None:
+                    db_ret = torch.empty(dy.shape[1], device=dy.device, dtype=torch.float32)
+                wsb = ARENA.get("bias", _lib.query("mvae_group_norm_bwd_dy_bias_workspace_bytes", dy.shape[1]), dy.device)
+                _lib.call("mvae_group_norm_bwd_dy_bias", cs.data_ptr(), rows, dy.shape[1],
+                          (bt if bt is not None else db_ret).data_ptr(), 1.0 if bt is not None else 0.0, wsb.data_ptr(),
+                          wsb.numel(), _stream(dy))
+                bias_done = True
         if side is not None:
             main.wait_event(ev_join)
         elif ctx.needs_input_grad[1]:
@@ -1661,7 +1796,9 @@ class GroupNormFn(torch.autograd.Function):
                 y_split: bool = False, grad_sink=None, part=None, link=None, dypack=None, lazy=None,
                 conv_dy_only: bool = False):
         _check(x, "group_norm input")
-        x = nhwc(x)
+        x_in, x = x, nhwc(x)
+        # (a deferred input gradient -- LazyGnGrad -- only for the input tensor itself, on the graph's first backward)
+        ctx.x_is_input, ctx.ran_bwd = x is x_in, False
         n, c, h, w = x.shape
         mean = torch.empty(n * groups, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
@@ -1752,6 +1889,30 @@ class GroupNormFn(torch.autograd.Function):
         # x is the output of the conv that requested the copy and has no other consumer: that conv reads the copy alone,
         # so the fp32 dx is left unwritten (its buffer is still autograd's gradient object)
         nodx = bool(ctx.conv_dy_only and DX_COPY_ONLY and req is not None and not bias_only and req.copy_ok)
+        if req is not None:
+            req.deferred = None  # (a placeholder of an earlier pass that never reached the conv)
+        # x is the output of a conv with no other consumer whose backward can compute this dx where it reads it, and this
+        # backward would now stream x and dy once more to write it (gn_dx_kernel): only the coefficient rows are
+        # computed, and the conv gets a placeholder carrying them (DeferredGnGrad). Not when anything else could read
+        # the gradient: retain_grad or a hook on x, a graph walked a second time, a pass that does not run the conv.
+        if (WINOGRAD_GNBWD_LOAD and gpart is not None and bias_only and req is not None and req.defer_ok and
+                ctx.conv_dy_only and add is None and ctx.x_is_input and not ctx.ran_bwd and not x.retains_grad and
+                not x._backward_hooks and _engine_runs(x.grad_fn)):
+            ctx.ran_bwd = True
+            coef = torch.empty(5 * n * c, device=x.device, dtype=torch.float32)
+            with _timed("gn_bwd", 0.0, (n, c, h * w)):
+                _lib.call("mvae_group_norm_bwd_part_coef_nhwc", gpart.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                          mean.data_ptr(), rstd.data_ptr(), _ptr(dg), _ptr(db), n, h * w, c, groups, ws.data_ptr(),
+                          ws.numel(), coef.data_ptr(), _stream(x))
+            ph = torch.full((1,), float("nan"), device=x.device).expand(n, c, h, w).as_subclass(DeferredGnGrad)
+            setattr(ph, GNB_LAZY_ATTR, LazyGnGrad(x, dy, coef, silu, gpart, gamma, beta, mean, rstd, groups))
+            req.deferred = ph
+            if ctx.needs_input_grad[1] and dg_ret is None:
+                _grad_done(ctx.gamma_ref)
+            if ctx.needs_input_grad[2] and db_ret is None:
+                _grad_done(ctx.beta_ref)
+            return ph, dg_ret, db_ret, None, None, None, None, None, None, None, None, None, None, None, None
+        ctx.ran_bwd = True
         dxp = None if nodx else dx.data_ptr()
         if nodx and DX_POISON:
             dx.fill_(float("nan"))  # (test aid: any kernel that still reads the unwritten dx turns the step NaN)
